@@ -9,7 +9,9 @@ Weights are seeded random tensors of the exact architecture (the checkpoints are
 synthetic 436-token prompt padded to 768 like sample_pipeline does, the speaker reference is a
 synthetic (1, 2560, 80) latent.
 
-    python bench.py --gpus 1 --steps 3 --warmup 1
+    python bench.py --gpus 1 --steps 3 --warmup 1                      (plain run: set-up, warm-up, the timed steps, the result line)
+    python bench.py --gpus 1 --steps 3 --warmup 1 --dump-outputs DIR   (+ the last timed step's latents / waveforms as DIR/<name>.npy)
+    python bench.py --full                                             (+ every sub-record named below; minutes instead of seconds)
     python bench.py --gpus N ...          (no torchrun environment: this process spawns the N ranks itself, before it touches the GPU)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
@@ -17,14 +19,15 @@ A step runs `--batch` (default 24; BASELINE config C3's per-GPU share is 4, `--b
 utterances through ONE sampler call, using the reference sampler's own batch axis (inference.py:448-449: text ids
 (B, Tt), speaker latents (B, Ts, 80), one noise draw of (B, S, 80)): the EchoDiT GEMMs then see M = 3*B*640 rows in
 the CFG steps and B*640 in the others, which is what fills 256 CUs with 256x256 tiles.  `--batch 1` is the
-single-request configuration (C2 proper); its throughput is measured in the same run and reported as
+single-request configuration (C2 proper); a `--full` run measures its throughput too and reports it as
 `single_request`.  `--concurrency` (default 2) such calls are kept in flight on separate HIP streams / engine contexts,
 as a serving process does with independent requests (handler.py:747-759): the second call's kernels fill the CUs that
 the last, partial round of 256x256 tiles of the first leaves idle (+6 % measured; `--concurrency 1` for one call).
 Measured sweep (audio-s/s, batch x concurrency, round-1 v7 binaries): 1x1 97, 4x1 134, 4x2 148, 8x2 157, 12x2 160, 16x2 161;
 round 2: 8x2 169-173, 12x2 172.6, 16x2 172.9, 8x3 169.6.
 
-Next to the headline the line carries: `single_request` (C2 proper: one utterance per call, with its own roofline fraction), `c3`
+A plain run times the headline only; the sub-records below are `null` in its line.  With `--full` the line carries next to the
+headline: `roofline` / `phases` (one more, profiled sampler call), `single_request` (C2 proper: one utterance per call, with its own roofline fraction), `c3`
 (BASELINE config C3: 4 mixed-length text_presets utterances per GPU, seeds = unit index, sharded over the ranks by
 `parallel.run_data_parallel_batched` and gathered in order on rank 0; `c3_share` is its N = 1 name), `c5` (BASELINE config C5: fp8
 operands, 100 Euler steps, its own roofline against the fp8 peak), `legacy_r1_workload` (round 1's definition of a step: 8 per call,
@@ -45,6 +48,7 @@ import os
 import sys
 import time
 
+import numpy as np
 import torch
 import torch.distributed as dist
 
@@ -258,6 +262,33 @@ def mixed_units(units, device):
     return ids.to(device), tmask, x0
 
 
+DUMP_BUDGET_BYTES = 60_000_000    # --dump-outputs writes at most this much (float32), all arrays together
+
+
+def dump_outputs(path: str, arrays, prefix: str = "") -> dict:
+    """Write what the last timed step returned to its caller as `path/<prefix><name>.npy` (float32).  `arrays` is a list of
+    (name, tensor).  The smallest arrays go out whole; one that does not fit its share of DUMP_BUDGET_BYTES goes out as a 1-D sample
+    of its flattened elements at sorted positions drawn from a generator seeded by its place in the list - the same positions in every
+    run and every build, so two dumps compare element for element."""
+    os.makedirs(path, exist_ok=True)
+    left, info = DUMP_BUDGET_BYTES // 4, {}
+    order = sorted(range(len(arrays)), key=lambda i: arrays[i][1].numel())
+    for k, i in enumerate(order):
+        name, t = arrays[i]
+        share = left // (len(order) - k)
+        flat = t.detach().reshape(-1)
+        if flat.numel() > share:
+            idx = torch.randint(flat.numel(), (share,), generator=torch.Generator().manual_seed(4242 + i)).sort().values
+            out = flat[idx.to(flat.device)]
+        else:
+            out = t.detach()
+        out = out.float().cpu().numpy()
+        np.save(os.path.join(path, prefix + name + ".npy"), out)
+        left -= out.size
+        info[prefix + name] = {"shape": list(t.shape), "written": list(out.shape), "sampled": out.size != t.numel()}
+    return info
+
+
 def free_port() -> int:
     import socket
     s = socket.socket()
@@ -297,6 +328,12 @@ def main() -> None:
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure every sub-record of the line (roofline / phases, single_request, c3, c5, legacy workload, CPU and eager-GPU "
+                         "baselines); without it the run does only what the headline figure needs and the --no-* switches below have nothing to switch off")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (per stream: the sampler's latents and the decoded waveforms) "
+                         "as DIR/<name>.npy, float32, at most 60 MB in all (larger arrays as a fixed, seeded sample of their elements)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-eager-baseline", action="store_true")
@@ -316,6 +353,10 @@ def main() -> None:
     ap.add_argument("--dist-backend", default=None, help="testing only: e.g. gloo to rehearse N ranks on one GPU")
     ap.add_argument("--force-device", type=int, default=None, help="testing only: every rank uses this cuda index")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:        # a plain run: set up, warm up, time the steps, print the line
+        args.no_cpu_baseline = args.no_eager_baseline = args.no_roofline = args.no_c5 = args.no_legs = True
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(spawn_ranks(args.gpus))             # no GPU call has happened in this process
@@ -360,12 +401,14 @@ def main() -> None:
     def make_step(ms, ds, kw):
         def step(seed: int):
             """One step: `conc` independent sampler calls of `nb` utterances + their decodes, each on its own stream and engine context."""
-            wavs = []
+            lats, wavs = [], []
             for c in range(len(ms)):
                 with torch.cuda.stream(streams[c]):
                     lat = E.sample_euler_cfg_independent_guidances(ms[c], spk, smask, ids, tmask, rng_seed=seed * conc + c, **kw)
                     last["latent"] = lat
+                    lats.append(lat)
                     wavs.append(E.ae_decode(ds[c], pca, lat))
+            last["latents"], last["wavs"] = lats, wavs
             return wavs[-1]
         return step
 
@@ -391,6 +434,10 @@ def main() -> None:
     if not bool(torch.isfinite(wav).all()):
         raise SystemExit(f"rank {rank}: non-finite waveform (latent finite: {bool(torch.isfinite(last['latent']).all())}, "
                          f"latent rms {float(last['latent'].float().pow(2).mean().sqrt()):.3g})")
+    dumped = None
+    if args.dump_outputs:    # the last timed step's results, every stream's; each rank writes its own (its seeds differ)
+        arrays = [(f"latent_s{c}", t) for c, t in enumerate(last["latents"])] + [(f"wav_s{c}", t) for c, t in enumerate(last["wavs"])]
+        dumped = dump_outputs(args.dump_outputs, arrays, prefix=f"rank{rank}_" if world > 1 else "")
 
     def roofline_of(m, d, kw, fp8: bool):
         """Live HIP-event timing of every GEMM launch of ONE sampler call of `nb` utterances (events on the launch stream)."""
@@ -605,6 +652,7 @@ def main() -> None:
                             "weight_broadcast": bcast or None},
             "roofline": roofline, "cpu_baseline": cpu, "eager_gpu_baseline": eager, "single_request": single,
             ("c3_share" if world == 1 else "c3"): c3, "c5": c5, "legacy_r1_workload": legacy, "phases": phases,
+            "full": bool(args.full), "dumped_outputs": dumped,
         }
         print(json.dumps(out))
     if world > 1:

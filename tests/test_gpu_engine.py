@@ -1245,7 +1245,7 @@ def test_bench_spawns_and_measures_two_ranks_end_to_end():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--dist-backend", "gloo", "--force-device", "0", "--steps", "1",
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--full", "--gpus", "2", "--dist-backend", "gloo", "--force-device", "0", "--steps", "1",
            "--warmup", "0", "--batch", "4", "--concurrency", "1", "--no-cpu-baseline", "--no-eager-baseline", "--no-c5"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])

@@ -223,6 +223,32 @@ def test_bench_host_logic(golden, monkeypatch):
     assert bench.dit_gemm_flops(1) > 1.3e14 and bench.free_port() > 0
 
 
+def test_bench_dump_outputs(tmp_path, monkeypatch):
+    """`bench.py --dump-outputs`: float32 .npy files, small arrays whole, an array over its share of the byte budget as a sample at
+    fixed positions (the same in every run, so two dumps compare element for element), the budget kept in all."""
+    import importlib.util
+    import numpy as np
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    assert bench.DUMP_BUDGET_BYTES <= 64 * 1000 * 1000
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 4 * 1000)
+    g = torch.Generator().manual_seed(0)
+    small = torch.randn((2, 5, 8), generator=g).bfloat16()
+    big = [torch.randn((3, 1, 700), generator=g) for _ in range(2)]
+    arrays = [("latent_s0", small), ("wav_s0", big[0]), ("wav_s1", big[1])]
+    info = bench.dump_outputs(str(tmp_path / "a"), arrays)
+    bench.dump_outputs(str(tmp_path / "b"), [(n, t.clone()) for n, t in arrays], prefix="rank1_")
+    got = {n: np.load(tmp_path / "a" / f"{n}.npy") for n, _ in arrays}
+    assert all(a.dtype == np.float32 for a in got.values()) and sum(a.nbytes for a in got.values()) <= 4000
+    assert np.array_equal(got["latent_s0"], small.float().numpy()) and info["latent_s0"] == {"shape": [2, 5, 8], "written": [2, 5, 8], "sampled": False}
+    for n, t in arrays[1:]:
+        assert info[n]["sampled"] and got[n].ndim == 1 and got[n].size == (1000 - 80) // 2
+        assert np.isin(got[n], t.numpy()).all()
+        assert np.array_equal(got[n], np.load(tmp_path / "b" / f"rank1_{n}.npy"))
+    assert not np.array_equal(got["wav_s0"], got["wav_s1"])
+
+
 def test_audio_io_host_side(tmp_path):
     """`load_audio`'s host half (reference inference.py:104-113; torchcodec / torchaudio are absent here, so this leg is PARITY UNPINNED and
     checked against its own published formula): the RIFF/WAVE parser round-trips every sample format through `wav_bytes`-style files,

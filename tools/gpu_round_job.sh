@@ -12,15 +12,15 @@ echo "pytest rc=$?" >> $O/gpu_tests.log
 grep -h "^FAILED\|^ERROR\| passed\| failed\|pytest rc" $O/gpu_tests.log | cut -c1-300
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1
 echo "smoke rc=$?" >> $O/smoke.log; tail -4 $O/smoke.log
-# 2. the bench line (default flags, as the driver runs it) with the per-shape table
-ECHO_PROFILE_SHAPES=1 timeout -k 10 1100 python bench.py > $O/bench.log 2> $O/bench.err
+# 2. the bench line with every sub-record (--full) and the per-shape table
+ECHO_PROFILE_SHAPES=1 timeout -k 10 1100 python bench.py --full > $O/bench.log 2> $O/bench.err
 tail -n 1 $O/bench.log > $O/${R}_bench_line_$V.json
 grep "^\[echo\] shape" $O/bench.err > $O/${R}_gemm_shapes_$V.txt || true
 head -c 400 $O/${R}_bench_line_$V.json; echo
 # 3. kernel trace of the same command (shorter run, no baselines / legs)
-timeout -k 10 700 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o run -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-eager-baseline --no-c5 --no-legs > $O/prof.log 2>&1
+timeout -k 10 700 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o run -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-eager-baseline --no-c5 --no-legs > $O/prof.log 2>&1
 rm -f $O/prof/*kernel_trace.csv $O/prof/*/*kernel_trace.csv
-python3 tools/summarize_prof.py $(ls $O/prof/*kernel_stats.csv $O/prof/*/*kernel_stats.csv 2>/dev/null | head -1) $O/${R}_bench_kernel_stats_$V.csv "rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-eager-baseline --no-c5 --no-legs (batch 24, 2 streams)"
+python3 tools/summarize_prof.py $(ls $O/prof/*kernel_stats.csv $O/prof/*/*kernel_stats.csv 2>/dev/null | head -1) $O/${R}_bench_kernel_stats_$V.csv "rocprofv3 --kernel-trace --stats -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-eager-baseline --no-c5 --no-legs (batch 24, 2 streams)"
 head -8 $O/${R}_bench_kernel_stats_$V.csv
 # 4. HBM-side traffic of the GEMM kernels: one counter per pass (MI355X_MICROARCH.md, HBM / rocprofv3), no tracing domains
 PMC_CMD="python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-eager-baseline --no-roofline"
