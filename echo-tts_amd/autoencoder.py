@@ -64,13 +64,45 @@ class DACConfig:
         return h
 
 
-def _fold(sd: Dict[str, torch.Tensor], p: str) -> torch.Tensor:
-    """Effective conv weight: plain `.weight`, or weight-norm parametrization folded once."""
+def _fold(sd: Dict[str, torch.Tensor], p: str, dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """Effective conv weight: plain `.weight`, or weight-norm parametrization folded once.
+
+    `dtype=torch.bfloat16` follows the reference's order of operations for a bf16 autoencoder (inference.py:62-66, autoencoder.py:90-94):
+    every checkpoint tensor is rounded to bf16 FIRST, the weight is then folded from the rounded `original0` / `original1` in bf16 on the host
+    with the expression the parametrization evaluates (`torch._weight_norm(v, g, 0)`), and only then reshaped by the caller."""
     if f"{p}.weight" in sd:
-        return sd[f"{p}.weight"].float()
-    g = sd[f"{p}.parametrizations.weight.original0"].float()
-    v = sd[f"{p}.parametrizations.weight.original1"].float()
+        return sd[f"{p}.weight"].to(dtype)
+    g = sd[f"{p}.parametrizations.weight.original0"].to(dtype)
+    v = sd[f"{p}.parametrizations.weight.original1"].to(dtype)
     return torch._weight_norm(v, g, 0)
+
+
+BF16_CHANNEL_STEP = 64      # K step of the bf16 taps-GEMM in elements: decoder channel counts of a bf16 DAC are carried at this pitch
+
+
+def _cpad(c: int, dtype: torch.dtype) -> int:
+    return -(-c // BF16_CHANNEL_STEP) * BF16_CHANNEL_STEP if dtype == torch.bfloat16 else c
+
+
+def _pad_dims(t: torch.Tensor, sizes: Dict[int, int]) -> torch.Tensor:
+    """Zero-pad the given dims of `t` up to `sizes[dim]` (no copy when nothing grows)."""
+    if all(t.shape[d] == n for d, n in sizes.items()):
+        return t
+    shape = list(t.shape)
+    for d, n in sizes.items():
+        shape[d] = n
+    out = torch.zeros(shape, dtype=t.dtype, device=t.device)
+    out[tuple(slice(0, n) for n in t.shape)] = t
+    return out
+
+
+def check_ae_dtype(dtype: Optional[torch.dtype]) -> torch.dtype:
+    """None / fp32 -> fp32 (the reference's default AE dtype), bf16 -> bf16, anything else is an error - never ignored."""
+    if dtype is None or dtype == torch.float32:
+        return torch.float32
+    if dtype == torch.bfloat16:
+        return torch.bfloat16
+    raise ValueError(f"the Fish S1-DAC runs in torch.float32 or torch.bfloat16, not {dtype}")
 
 
 def _conv_as_gemm(w: torch.Tensor) -> torch.Tensor:
@@ -98,10 +130,82 @@ def ae_rope_cache(seq_len: int, n_elem: int, base: float = 10000.0) -> torch.Ten
     return torch.stack([cis.real, cis.imag], dim=-1).to(torch.bfloat16).float().contiguous()
 
 
-class DAC:
-    """Decode-only Fish S1-DAC on libechohip (fp32 activations and fp32 MFMA, the reference's default AE dtype)."""
+def decode_tensors(c: DACConfig, sd: Dict[str, torch.Tensor], dtype: torch.dtype = torch.float32):
+    """(engine name, host tensor of `dtype`) for every decode-path tensor, as echo_finalize_dac expects them: weight-norm folded, conv kernels in
+    GEMM form.  fp32: the checkpoint values.  bf16: every tensor rounded first, folded in bf16 (_fold), and every decoder channel count zero-padded
+    to BF16_CHANNEL_STEP (weights on both channel axes, biases and Snake alphas alike) before the GEMM reshape - the padding columns are real zeros."""
+    out = []
+    if dtype == torch.bfloat16:      # the bf16 fold is a host computation (the fixture's bits): a state dict on the device comes back first
+        sd = {k: (v.cpu() if v.is_cuda else v) for k, v in sd.items() if k.startswith(("decoder.", "quantizer.post_module.", "quantizer.upsample."))}
 
-    def __init__(self, config, state_dict: Dict[str, torch.Tensor], device: str | torch.device = "cuda:0"):
+    def put(name, t):
+        out.append((name, t.to(dtype)))
+
+    def P(n):
+        return _cpad(n, dtype)
+
+    pm = "quantizer.post_module"
+    for i in range(c.post_layers):
+        lp = f"{pm}.layers.{i}"
+        for n in ("attention.wqkv.weight", "attention.wo.weight", "feed_forward.w1.weight", "feed_forward.w3.weight",
+                  "feed_forward.w2.weight", "ffn_norm.weight", "attention_norm.weight", "attention_layer_scale.gamma",
+                  "ffn_layer_scale.gamma"):
+            put(f"{lp}.{n}", sd[f"{lp}.{n}"])
+    put(f"{pm}.norm.weight", sd[f"{pm}.norm.weight"])
+    ups = list(reversed(c.upsample_factors))
+    for i, f in enumerate(ups):
+        up = f"quantizer.upsample.{i}"
+        put(f"{up}.0.conv.weight", _convT_as_gemm(_fold(sd, f"{up}.0.conv", dtype), f))
+        put(f"{up}.0.conv.bias", sd[f"{up}.0.conv.bias"])
+        put(f"{up}.1.dwconv.conv.weight", _fold(sd, f"{up}.1.dwconv.conv", dtype))
+        for n in ("dwconv.conv.bias", "norm.weight", "norm.bias", "pwconv1.weight", "pwconv1.bias", "pwconv2.weight",
+                  "pwconv2.bias", "gamma"):
+            put(f"{up}.1.{n}", sd[f"{up}.1.{n}"])
+    dm = "decoder.model"
+    ch = c.decoder_dim
+
+    def vec(key, n):
+        return _pad_dims(sd[key].to(dtype).flatten(), {0: P(n)})
+
+    put(f"{dm}.0.conv.weight", _conv_as_gemm(_pad_dims(_fold(sd, f"{dm}.0.conv", dtype), {0: P(ch)})))
+    put(f"{dm}.0.conv.bias", vec(f"{dm}.0.conv.bias", ch))
+    for i, r in enumerate(c.decoder_rates):
+        ci, co = ch >> i, ch >> (i + 1)
+        bp = f"{dm}.{i + 1}.block"
+        put(f"{bp}.0.alpha", vec(f"{bp}.0.alpha", ci))
+        put(f"{bp}.1.conv.weight", _convT_as_gemm(_pad_dims(_fold(sd, f"{bp}.1.conv", dtype), {0: P(ci), 1: P(co)}), r))
+        put(f"{bp}.1.conv.bias", vec(f"{bp}.1.conv.bias", co))
+        for j in range(3):
+            rp = f"{bp}.{2 + j}.block"
+            put(f"{rp}.0.alpha", vec(f"{rp}.0.alpha", co))
+            put(f"{rp}.1.conv.weight", _conv_as_gemm(_pad_dims(_fold(sd, f"{rp}.1.conv", dtype), {0: P(co), 1: P(co)})))
+            put(f"{rp}.1.conv.bias", vec(f"{rp}.1.conv.bias", co))
+            put(f"{rp}.2.alpha", vec(f"{rp}.2.alpha", co))
+            put(f"{rp}.3.conv.weight", _conv_as_gemm(_pad_dims(_fold(sd, f"{rp}.3.conv", dtype), {0: P(co), 1: P(co)})))
+            put(f"{rp}.3.conv.bias", vec(f"{rp}.3.conv.bias", co))
+    n = len(c.decoder_rates)
+    cl = ch >> n
+    put(f"{dm}.{n + 1}.alpha", vec(f"{dm}.{n + 1}.alpha", cl))
+    wout = _pad_dims(_fold(sd, f"{dm}.{n + 2}.conv", dtype), {1: P(cl)})              # (1, C, 7) -> (7, C)
+    put(f"{dm}.{n + 2}.conv.weight", wout[0].t().contiguous())
+    put(f"{dm}.{n + 2}.conv.bias", sd[f"{dm}.{n + 2}.conv.bias"])
+    return out
+
+
+class DAC:
+    """Fish S1-DAC on libechohip.
+
+    `dtype=torch.float32` (default, the reference's default AE dtype): fp32 weights and activations on the split-3 / fp32 MFMA.
+    `dtype=torch.bfloat16` (the dtype the reference serves its AE in, handler.py:345): the DECODE path - `decode_zq`, `decode_latent`,
+    `decode_latent_tail` / `DACStream`, `ae_decode` - runs on bf16 weights and channels-last bf16 activations with fp32 accumulation.  Call
+    signatures and I/O dtypes do not change: inputs are fp32 (`decode_zq` rounds `z_q` to bf16 as `z_q.to(fish_ae.dtype)` does, `ae_decode`
+    computes the PCA inverse in fp32 and rounds once), waveforms come back as fp32 tensors holding bf16-representable values.
+    The ENCODE path (`encode`, `encode_zq`, `encode_latent`) of a bf16 `DAC` keeps the fp32 weights and kernels: a bf16 VQ argmax flips codes,
+    which is a separate piece of work.  Any other dtype raises ValueError."""
+
+    def __init__(self, config, state_dict: Dict[str, torch.Tensor], device: str | torch.device = "cuda:0",
+                 dtype: Optional[torch.dtype] = torch.float32):
+        self._dtype = check_ae_dtype(dtype)
         self.config = DACConfig.from_any(config)
         self._device = torch.device(device)
         if self._device.type != "cuda":
@@ -109,7 +213,7 @@ class DAC:
         self._lib = L.load_library()
         c = self.config
         cfg = L.EchoConfig()
-        cfg.precision = L.ECHO_F32
+        cfg.precision = L.ECHO_BF16 if self._dtype == torch.bfloat16 else L.ECHO_F32
         cfg.latent_size = c.latent_size
         cfg.dac_latent_dim, cfg.dac_decoder_dim, cfg.dac_n_rates = c.latent_dim, c.decoder_dim, len(c.decoder_rates)
         for i, r in enumerate(c.decoder_rates):
@@ -161,7 +265,7 @@ class DAC:
 
     @property
     def dtype(self) -> torch.dtype:
-        return torch.float32
+        return self._dtype
 
     def eval(self) -> "DAC":
         return self
@@ -169,52 +273,15 @@ class DAC:
     def _stream(self) -> int:
         return torch.cuda.current_stream(self._device).cuda_stream
 
-    def _put(self, name: str, t: torch.Tensor) -> None:
-        t = t.detach().float().contiguous()
+    def _put(self, name: str, t: torch.Tensor, dtype: torch.dtype = torch.float32) -> None:
+        t = t.detach().to(dtype).contiguous()
         shape = (L.c_i64 * max(t.dim(), 1))(*(list(t.shape) or [1]))
-        L.check(self._lib.echo_load_tensor(self._ctx, name.encode(), t.data_ptr(), L.ECHO_F32, max(t.dim(), 1), shape,
-                                           int(t.is_cuda)), self._ctx)
+        code = L.ECHO_BF16 if dtype == torch.bfloat16 else L.ECHO_F32
+        L.check(self._lib.echo_load_tensor(self._ctx, name.encode(), t.data_ptr(), code, max(t.dim(), 1), shape, int(t.is_cuda)), self._ctx)
 
     def _load(self, sd: Dict[str, torch.Tensor]) -> None:
-        c = self.config
-        pm = "quantizer.post_module"
-        for i in range(c.post_layers):
-            lp = f"{pm}.layers.{i}"
-            for n in ("attention.wqkv.weight", "attention.wo.weight", "feed_forward.w1.weight", "feed_forward.w3.weight",
-                      "feed_forward.w2.weight", "ffn_norm.weight", "attention_norm.weight", "attention_layer_scale.gamma",
-                      "ffn_layer_scale.gamma"):
-                self._put(f"{lp}.{n}", sd[f"{lp}.{n}"])
-        self._put(f"{pm}.norm.weight", sd[f"{pm}.norm.weight"])
-        ups = list(reversed(c.upsample_factors))
-        for i, f in enumerate(ups):
-            up = f"quantizer.upsample.{i}"
-            self._put(f"{up}.0.conv.weight", _convT_as_gemm(_fold(sd, f"{up}.0.conv"), f))
-            self._put(f"{up}.0.conv.bias", sd[f"{up}.0.conv.bias"])
-            self._put(f"{up}.1.dwconv.conv.weight", _fold(sd, f"{up}.1.dwconv.conv"))
-            for n in ("dwconv.conv.bias", "norm.weight", "norm.bias", "pwconv1.weight", "pwconv1.bias", "pwconv2.weight",
-                      "pwconv2.bias", "gamma"):
-                self._put(f"{up}.1.{n}", sd[f"{up}.1.{n}"])
-        dm = "decoder.model"
-        self._put(f"{dm}.0.conv.weight", _conv_as_gemm(_fold(sd, f"{dm}.0.conv")))
-        self._put(f"{dm}.0.conv.bias", sd[f"{dm}.0.conv.bias"])
-        for i, r in enumerate(c.decoder_rates):
-            bp = f"{dm}.{i + 1}.block"
-            self._put(f"{bp}.0.alpha", sd[f"{bp}.0.alpha"].flatten())
-            self._put(f"{bp}.1.conv.weight", _convT_as_gemm(_fold(sd, f"{bp}.1.conv"), r))
-            self._put(f"{bp}.1.conv.bias", sd[f"{bp}.1.conv.bias"])
-            for j in range(3):
-                rp = f"{bp}.{2 + j}.block"
-                self._put(f"{rp}.0.alpha", sd[f"{rp}.0.alpha"].flatten())
-                self._put(f"{rp}.1.conv.weight", _conv_as_gemm(_fold(sd, f"{rp}.1.conv")))
-                self._put(f"{rp}.1.conv.bias", sd[f"{rp}.1.conv.bias"])
-                self._put(f"{rp}.2.alpha", sd[f"{rp}.2.alpha"].flatten())
-                self._put(f"{rp}.3.conv.weight", _conv_as_gemm(_fold(sd, f"{rp}.3.conv")))
-                self._put(f"{rp}.3.conv.bias", sd[f"{rp}.3.conv.bias"])
-        n = len(c.decoder_rates)
-        self._put(f"{dm}.{n + 1}.alpha", sd[f"{dm}.{n + 1}.alpha"].flatten())
-        wout = _fold(sd, f"{dm}.{n + 2}.conv")                       # (1, C, 7) -> (7, C)
-        self._put(f"{dm}.{n + 2}.conv.weight", wout[0].t().contiguous())
-        self._put(f"{dm}.{n + 2}.conv.bias", sd[f"{dm}.{n + 2}.conv.bias"])
+        for name, t in decode_tensors(self.config, sd, self._dtype):
+            self._put(name, t, self._dtype)
         L.check(self._lib.echo_finalize_dac(self._ctx, self._stream()), self._ctx)
 
     def _load_encoder(self, sd: Dict[str, torch.Tensor]) -> None:

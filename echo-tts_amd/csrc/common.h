@@ -240,6 +240,8 @@ template <typename T> hipError_t launch_euler(const EulerArgs& e, hipStream_t st
 hipError_t launch_softmax_f32(float* s, long ld, int rows_per_batch, int nbatch, int ncols, int ncols_pad,
                               const float* bias, long bias_batch_stride, int heads_per_bias_row,
                               int causal, int window, hipStream_t st);
+// the same causal-window softmax on bf16 scores, in place: fp32 arithmetic from one read, probabilities rounded once at the store
+hipError_t launch_softmax_window_bf16(bf16_t* s, long ld, int rows_per_batch, int nbatch, int ncols, int ncols_pad, int window, hipStream_t st);
 hipError_t launch_mask_to_bias(const uint8_t* mask, float* bias, long n, hipStream_t st);
 
 // ---------------------------------------------------------------- post-processing (postproc.hip)
@@ -258,10 +260,15 @@ hipError_t launch_resample(const float* x, long n, const float* bank, int taps, 
 
 // ---------------------------------------------------------------- DAC helpers (dac.hip)
 // All take channels-last fp32 activations x[t][c]; S = time steps per batch item (causal padding restarts there).
-hipError_t launch_ae_rope(float* x, long ldx, int rows, int S, int H, int HD, const float* cache /*(pos,HD/2,2)*/, hipStream_t st);
-hipError_t launch_dwconv_ln(const float* x, long ldx, float* y, long ldy, int T, int S, int C, const float* w /*(C,7)*/,
-                            const float* b, const float* lnw, const float* lnb, float eps, hipStream_t st);
-hipError_t launch_conv_out_tanh(const float* x, long ldx, float* y, long T, int S, int C, int k, const float* w /*(k,C)*/,
+// E = float or bf16_t (the bf16 DAC decoder: bf16 activations and weights, fp32 arithmetic, one rounding per materialised tensor).
+template <typename E>
+hipError_t launch_ae_rope(E* x, long ldx, int rows, int S, int H, int HD, const float* cache /*(pos,HD/2,2)*/, hipStream_t st);
+template <typename E>
+hipError_t launch_dwconv_ln(const E* x, long ldx, E* y, long ldy, int T, int S, int C, const E* w /*(C,7)*/,
+                            const E* b, const E* lnw, const E* lnb, float eps, hipStream_t st);
+// y is the fp32 waveform in both cases (bf16: bf16-representable values)
+template <typename E>
+hipError_t launch_conv_out_tanh(const E* x, long ldx, float* y, long T, int S, int C, int k, const E* w /*(k,C)*/,
                                 float bias, hipStream_t st);
 hipError_t launch_pca_prep(const float* lat, float* out, long ldo, long rows, int L, int Lpad, float scale, hipStream_t st);
 hipError_t launch_presplit_w(float* w, long rows, long ld, hipStream_t st);

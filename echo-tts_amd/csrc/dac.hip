@@ -5,7 +5,8 @@
 namespace {
 
 // autoencoder.py:815-826: interleaved pairs, cos/sin cache (pos, HD/2, 2) (bf16-rounded values, held as fp32)
-__global__ void ae_rope_kernel(float* __restrict__ x, long ldx, long rows, int S, int H, int HD, const float* __restrict__ cache) {
+template <typename T>
+__global__ void ae_rope_kernel(T* __restrict__ x, long ldx, long rows, int S, int H, int HD, const float* __restrict__ cache) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   const int half = HD >> 1;
   const long n = rows * H * half;
@@ -14,18 +15,22 @@ __global__ void ae_rope_kernel(float* __restrict__ x, long ldx, long rows, int S
   const int rem = (int)(i - row * (H * half));
   const int h = rem / half, j = rem - h * half;
   const int pos = (int)(row % S);
-  float* p = x + row * ldx + h * HD + 2 * j;
+  T* p = x + row * ldx + h * HD + 2 * j;
   const float c = cache[((long)pos * half + j) * 2], s = cache[((long)pos * half + j) * 2 + 1];
-  const float a = p[0], b = p[1];
-  p[0] = __fsub_rn(__fmul_rn(a, c), __fmul_rn(b, s));
-  p[1] = __fadd_rn(__fmul_rn(b, c), __fmul_rn(a, s));
+  const float a = Num<T>::ld(p[0]), b = Num<T>::ld(p[1]);
+  p[0] = Num<T>::st(__fsub_rn(__fmul_rn(a, c), __fmul_rn(b, s)));
+  p[1] = Num<T>::st(__fadd_rn(__fmul_rn(b, c), __fmul_rn(a, s)));
 }
 
 // ConvNeXtBlock front half (autoencoder.py:362-364): causal depthwise conv k7 (+bias), then LayerNorm over C.
 // One wave per time step; lane owns float4 chunks lane + 64j.
-__global__ void __launch_bounds__(256) dwconv_ln_kernel(const float* __restrict__ x, long ldx, float* __restrict__ y, long ldy, int T, int S,
-                                                        int C, const float* __restrict__ w, const float* __restrict__ b,
-                                                        const float* __restrict__ lnw, const float* __restrict__ lnb, float eps) {
+// E = bf16: activations and weights are bf16, the arithmetic stays fp32; the conv output is rounded to bf16 before the LayerNorm
+// (the tensor the reference materialises between the two modules), the result once at the store.
+template <typename E>
+__global__ void __launch_bounds__(256) dwconv_ln_kernel(const E* __restrict__ x, long ldx, E* __restrict__ y, long ldy, int T, int S,
+                                                        int C, const E* __restrict__ w, const E* __restrict__ b,
+                                                        const E* __restrict__ lnw, const E* __restrict__ lnb, float eps) {
+  typedef Vec4<E> V;
   const int lane = threadIdx.x & 63;
   const long t = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (t >= T) return;
@@ -38,19 +43,19 @@ __global__ void __launch_bounds__(256) dwconv_ln_kernel(const float* __restrict_
   for (int c = 0; c < MAXC; ++c) {
     const int ch = lane + 64 * c;
     if (ch < nch) {
-      const float4 bb = *(const float4*)(b + ch * 4);
-      float acc[4] = {bb.x, bb.y, bb.z, bb.w};
+      float acc[4];
+      V::unpack(*(const typename V::raw*)(b + ch * 4), acc);
 #pragma unroll
       for (int k = 0; k < 7; ++k) {
         const int dt = k - 6;
         if (tl + dt < 0) continue;
-        const float4 xv = *(const float4*)(x + (t + dt) * ldx + ch * 4);
-        const float xs[4] = {xv.x, xv.y, xv.z, xv.w};
+        float xs[4];
+        V::unpack(*(const typename V::raw*)(x + (t + dt) * ldx + ch * 4), xs);
 #pragma unroll
-        for (int i = 0; i < 4; ++i) acc[i] = fmaf(w[(ch * 4 + i) * 7 + k], xs[i], acc[i]);
+        for (int i = 0; i < 4; ++i) acc[i] = fmaf(Num<E>::ld(w[(ch * 4 + i) * 7 + k]), xs[i], acc[i]);
       }
 #pragma unroll
-      for (int i = 0; i < 4; ++i) { v[c][i] = acc[i]; s1 += acc[i]; }
+      for (int i = 0; i < 4; ++i) { v[c][i] = Num<E>::rnd(acc[i]); s1 += v[c][i]; }
     }
   }
   const float mean = wave_sum(s1) / (float)C;
@@ -68,13 +73,14 @@ __global__ void __launch_bounds__(256) dwconv_ln_kernel(const float* __restrict_
   for (int c = 0; c < MAXC; ++c) {
     const int ch = lane + 64 * c;
     if (ch < nch) {
-      const float4 g = *(const float4*)(lnw + ch * 4), be = *(const float4*)(lnb + ch * 4);
-      float4 o;
-      o.x = (v[c][0] - mean) * rs * g.x + be.x;
-      o.y = (v[c][1] - mean) * rs * g.y + be.y;
-      o.z = (v[c][2] - mean) * rs * g.z + be.z;
-      o.w = (v[c][3] - mean) * rs * g.w + be.w;
-      *(float4*)(y + t * ldy + ch * 4) = o;
+      float g[4], be[4], o[4];
+      V::unpack(*(const typename V::raw*)(lnw + ch * 4), g);
+      V::unpack(*(const typename V::raw*)(lnb + ch * 4), be);
+      o[0] = (v[c][0] - mean) * rs * g[0] + be[0];
+      o[1] = (v[c][1] - mean) * rs * g[1] + be[1];
+      o[2] = (v[c][2] - mean) * rs * g[2] + be[2];
+      o[3] = (v[c][3] - mean) * rs * g[3] + be[3];
+      *(typename V::raw*)(y + t * ldy + ch * 4) = V::pack(o);
     }
   }
 }
@@ -84,8 +90,11 @@ __global__ void __launch_bounds__(256) dwconv_ln_kernel(const float* __restrict_
 // accumulates the k per-tap partial dot products of its columns, an 8-lane butterfly finishes them into LDS
 // d[row][tap], and the outputs of the block are y[t] = tanh(bias + sum_tap d[t - (k-1) + tap][tap]).
 constexpr int CO_ROWS = 128, CO_KMAX = 8, CO_NV = 4;
-__global__ void __launch_bounds__(256) conv_out_tanh_kernel(const float* __restrict__ x, long ldx, float* __restrict__ y, long T, int S,
-                                                            int C, int k, const float* __restrict__ w, float bias) {
+// E = bf16: x and w are bf16, y stays the caller's fp32 waveform buffer and receives bf16-representable values.
+template <typename E>
+__global__ void __launch_bounds__(256) conv_out_tanh_kernel(const E* __restrict__ x, long ldx, float* __restrict__ y, long T, int S,
+                                                            int C, int k, const E* __restrict__ w, float bias) {
+  typedef Vec4<E> V;
   __shared__ float d[CO_ROWS][CO_KMAX];
   const int R = CO_ROWS - (k - 1);                       // outputs per block
   const long t0 = (long)blockIdx.x * R;
@@ -96,7 +105,9 @@ __global__ void __launch_bounds__(256) conv_out_tanh_kernel(const float* __restr
 #pragma unroll
     for (int v = 0; v < CO_NV; ++v) {
       const int c = (j + 8 * v) * 4;
-      wr[kk][v] = (kk < k && c < C) ? *(const float4*)(w + (long)kk * C + c) : make_float4(0.f, 0.f, 0.f, 0.f);
+      float wv[4] = {0.f, 0.f, 0.f, 0.f};
+      if (kk < k && c < C) V::unpack(*(const typename V::raw*)(w + (long)kk * C + c), wv);
+      wr[kk][v] = make_float4(wv[0], wv[1], wv[2], wv[3]);
     }
 #pragma unroll 1
   for (int it = 0; it < CO_ROWS / 32; ++it) {
@@ -110,7 +121,9 @@ __global__ void __launch_bounds__(256) conv_out_tanh_kernel(const float* __restr
       for (int v = 0; v < CO_NV; ++v) {
         const int c = (j + 8 * v) * 4;
         if (c < C) {
-          const float4 xv = *(const float4*)(x + t * ldx + c);
+          float xs[4];
+          V::unpack(*(const typename V::raw*)(x + t * ldx + c), xs);
+          const float4 xv = make_float4(xs[0], xs[1], xs[2], xs[3]);
 #pragma unroll
           for (int kk = 0; kk < CO_KMAX; ++kk) {
             acc[kk] = fmaf(xv.x, wr[kk][v].x, acc[kk]); acc[kk] = fmaf(xv.y, wr[kk][v].y, acc[kk]);
@@ -134,7 +147,7 @@ __global__ void __launch_bounds__(256) conv_out_tanh_kernel(const float* __restr
     float a = bias;
     for (int kk = 0; kk < k; ++kk)
       if (tl + kk - (k - 1) >= 0) a += d[i + kk][kk];
-    y[t] = tanhf(a);
+    y[t] = Num<E>::rnd(tanhf(Num<E>::rnd(a)));
   }
 }
 
@@ -247,22 +260,25 @@ hipError_t launch_vq_argmax(const float* e, long lde, int T, const float* cbn, c
   return hipGetLastError();
 }
 
-hipError_t launch_ae_rope(float* x, long ldx, int rows, int S, int H, int HD, const float* cache, hipStream_t st) {
+template <typename T>
+hipError_t launch_ae_rope(T* x, long ldx, int rows, int S, int H, int HD, const float* cache, hipStream_t st) {
   const long n = (long)rows * H * (HD / 2);
-  hipLaunchKernelGGL(ae_rope_kernel, grid1d(n), dim3(256), 0, st, x, ldx, (long)rows, S, H, HD, cache);
+  hipLaunchKernelGGL(ae_rope_kernel<T>, grid1d(n), dim3(256), 0, st, x, ldx, (long)rows, S, H, HD, cache);
   return hipGetLastError();
 }
-hipError_t launch_dwconv_ln(const float* x, long ldx, float* y, long ldy, int T, int S, int C, const float* w, const float* b,
-                            const float* lnw, const float* lnb, float eps, hipStream_t st) {
-  if (C % 4 || C > 1024) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(dwconv_ln_kernel, dim3((T + 3) / 4), dim3(256), 0, st, x, ldx, y, ldy, T, S, C, w, b, lnw, lnb, eps);
+template <typename E>
+hipError_t launch_dwconv_ln(const E* x, long ldx, E* y, long ldy, int T, int S, int C, const E* w, const E* b,
+                            const E* lnw, const E* lnb, float eps, hipStream_t st) {
+  if (C % 4 || C > 1024 || (ldx & 3) || (ldy & 3)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(dwconv_ln_kernel<E>, dim3((T + 3) / 4), dim3(256), 0, st, x, ldx, y, ldy, T, S, C, w, b, lnw, lnb, eps);
   return hipGetLastError();
 }
-hipError_t launch_conv_out_tanh(const float* x, long ldx, float* y, long T, int S, int C, int k, const float* w, float bias,
+template <typename E>
+hipError_t launch_conv_out_tanh(const E* x, long ldx, float* y, long T, int S, int C, int k, const E* w, float bias,
                                 hipStream_t st) {
   if (C % 4 || C > 32 * CO_NV || k < 1 || k > CO_KMAX || (ldx & 3)) return hipErrorInvalidValue;
   const int R = CO_ROWS - (k - 1);
-  hipLaunchKernelGGL(conv_out_tanh_kernel, dim3((unsigned)((T + R - 1) / R)), dim3(256), 0, st, x, ldx, y, T, S, C, k, w, bias);
+  hipLaunchKernelGGL(conv_out_tanh_kernel<E>, dim3((unsigned)((T + R - 1) / R)), dim3(256), 0, st, x, ldx, y, T, S, C, k, w, bias);
   return hipGetLastError();
 }
 hipError_t launch_pca_prep(const float* lat, float* out, long ldo, long rows, int L, int Lpad, float scale, hipStream_t st) {
@@ -273,3 +289,12 @@ hipError_t launch_snake_f32(const float* x, long ldx, float* y, long ldy, long r
   hipLaunchKernelGGL(snake_kernel, grid1d(rows * C), dim3(256), 0, st, x, ldx, y, ldy, rows, C, alpha);
   return hipGetLastError();
 }
+
+template hipError_t launch_ae_rope<float>(float*, long, int, int, int, int, const float*, hipStream_t);
+template hipError_t launch_ae_rope<bf16_t>(bf16_t*, long, int, int, int, int, const float*, hipStream_t);
+template hipError_t launch_dwconv_ln<float>(const float*, long, float*, long, int, int, int, const float*, const float*, const float*, const float*,
+                                            float, hipStream_t);
+template hipError_t launch_dwconv_ln<bf16_t>(const bf16_t*, long, bf16_t*, long, int, int, int, const bf16_t*, const bf16_t*, const bf16_t*,
+                                             const bf16_t*, float, hipStream_t);
+template hipError_t launch_conv_out_tanh<float>(const float*, long, float*, long, int, int, int, const float*, float, hipStream_t);
+template hipError_t launch_conv_out_tanh<bf16_t>(const bf16_t*, long, float*, long, int, int, int, const bf16_t*, float, hipStream_t);

@@ -344,6 +344,27 @@ __global__ void __launch_bounds__(256) softmax_f32_kernel(float* __restrict__ s,
   for (int c = lane; c < ncols_pad; c += 64) p[c] = c < ncols ? p[c] * inv : 0.0f;
 }
 
+// bf16 scores of the Fish S1-DAC post_module (bf16 decoder): causal window, every pass re-reads the bf16 score and works in fp32;
+// the only rounding is the probability's at the store.  Columns ncols..ncols_pad-1 (the K padding of the P.V GEMM) are written as zeros.
+__global__ void __launch_bounds__(256) softmax_window_bf16_kernel(bf16_t* __restrict__ s, long ld, int rows_per_batch, long total_rows, int ncols,
+                                                                  int ncols_pad, int window) {
+  const int lane = threadIdx.x & 63;
+  const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= total_rows) return;
+  const int qi = (int)(row % rows_per_batch);
+  bf16_t* p = s + row * ld;
+  const int c_lo = window > 0 && qi - window + 1 > 0 ? qi - window + 1 : 0;
+  const int c_hi = qi < ncols - 1 ? qi : ncols - 1;      // inclusive
+  float mx = -INFINITY;
+  for (int c = c_lo + lane; c <= c_hi; c += 64) mx = fmaxf(mx, bf2f(p[c]));
+  mx = wave_max(mx);
+  float sum = 0.f;
+  for (int c = c_lo + lane; c <= c_hi; c += 64) sum += expf(bf2f(p[c]) - mx);
+  sum = wave_sum(sum);
+  const float inv = 1.0f / sum;
+  for (int c = lane; c < ncols_pad; c += 64) p[c] = (c >= c_lo && c <= c_hi) ? f2bf(expf(bf2f(p[c]) - mx) * inv) : (bf16_t)0;
+}
+
 __global__ void mask_to_bias_kernel(const uint8_t* __restrict__ m, float* __restrict__ b, long n) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) b[i] = m[i] ? 0.0f : -INFINITY;
@@ -617,6 +638,13 @@ hipError_t launch_softmax_f32(float* s, long ld, int rows_per_batch, int nbatch,
   const long total = (long)rows_per_batch * nbatch;
   hipLaunchKernelGGL(softmax_f32_kernel, dim3((unsigned)((total + 3) / 4)), dim3(256), 0, st, s, ld, rows_per_batch, total, ncols,
                      ncols_pad, bias, bias_batch_stride, heads_per_bias_row < 1 ? 1 : heads_per_bias_row, causal, window);
+  return hipGetLastError();
+}
+hipError_t launch_softmax_window_bf16(bf16_t* s, long ld, int rows_per_batch, int nbatch, int ncols, int ncols_pad, int window, hipStream_t st) {
+  const long total = (long)rows_per_batch * nbatch;
+  if (total < 1 || ncols < 1 || ncols_pad < ncols || ncols_pad > ld) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(softmax_window_bf16_kernel, dim3((unsigned)((total + 3) / 4)), dim3(256), 0, st, s, ld, rows_per_batch, total, ncols, ncols_pad,
+                     window);
   return hipGetLastError();
 }
 hipError_t launch_norm_adaln_fp8(const void* x, long ldx, void* q, long ldq, float* scale, int rows, int D, float eps, const void* scale1p,

@@ -1076,8 +1076,8 @@ struct Engine : EngineBase {
       long maxel = (long)T_dac * upf * std::max(C * 4, cfg.dac_decoder_dim);
       long rows = (long)T_dac * upf;
       for (auto& b : dblocks) { rows *= b.r; maxel = std::max(maxel, rows * b.co); }
-      const long PADF = 64L * std::max(cfg.dac_decoder_dim, 4 * C);
-      const size_t bytes = (size_t)(maxel + PADF + 128L * 4 * C) * sizeof(float);
+      const long PADF = dac_padf();
+      const size_t bytes = (size_t)(maxel + PADF + 128L * 4 * C) * sizeof(T);
       CK(b_dacA.reserve(bytes)); CK(b_dacB.reserve(bytes)); CK(b_dacC.reserve(bytes));
     }
     return ECHO_OK;
@@ -1410,35 +1410,55 @@ struct Engine : EngineBase {
     }
   }
 
-  // ------------------------------------------------------------------ Fish S1-DAC decode (fp32 weights/activations)
-  struct DacLayer { float *wqkv, *wo, *w13, *w2, *an, *fn, *ga, *gf; };
-  struct DacUp { float *w, *b, *dw, *db, *lnw, *lnb, *p1w, *p1b, *p2w, *p2b, *gamma; int f; };
-  struct DacRU { float *a0, *w7, *b7, *a1, *w1, *b1; };
-  struct DacBlock { float *alpha, *wt, *bt; DacRU ru[3]; int ci, co, r; };
-  std::vector<DacLayer> dpost; float* dpost_norm = nullptr;
-  std::vector<DacUp> dups;
-  float *dconv0_w = nullptr, *dconv0_b = nullptr, *dfinal_alpha = nullptr, *dout_w = nullptr, *pca_w = nullptr, *pca_b = nullptr;
+  // ------------------------------------------------------------------ Fish S1-DAC decode
+  // The decode path runs in the context's precision T: fp32 weights / activations on the split-3 (or exact fp32) MFMA, or - ECHO_BF16 - bf16 weights
+  // and channels-last bf16 activations on the native bf16 MFMA (the reference's own AE dtype, handler.py:345).  The encode path below keeps fp32
+  // weights and kernels in every context (X = float).  bf16: every channel count of the decoder is carried at a row pitch rounded up to the
+  // 64-element K step (cpad; 96 -> 128, the tiny config's 32 -> 64): the loader zero-pads weights, biases and alphas, so the padding columns are
+  // written as real zeros by every epilogue (acc 0 + bias 0 + residual 0, snake(0) = 0) and contribute nothing as K columns.
+  template <typename X> struct DacLayerT { X *wqkv, *wo, *w13, *w2, *an, *fn, *ga, *gf; };
+  template <typename X> struct DacUpT { X *w, *b, *dw, *db, *lnw, *lnb, *p1w, *p1b, *p2w, *p2b, *gamma; int f; };
+  typedef DacLayerT<float> DacLayer;      // encode path
+  typedef DacUpT<float> DacUp;
+  struct DacRU { T *a0, *w7, *b7, *a1, *w1, *b1; };
+  struct DacBlock { T *alpha, *wt, *bt; DacRU ru[3]; int ci, co, r; };     // ci / co: padded channel counts (cpad)
+  std::vector<DacLayerT<T>> dpost; T* dpost_norm = nullptr;
+  std::vector<DacUpT<T>> dups;
+  T *dconv0_w = nullptr, *dconv0_b = nullptr, *dfinal_alpha = nullptr, *dout_w = nullptr;
+  float *pca_w = nullptr, *pca_b = nullptr;      // the PCA inverse stays fp32 in both precisions (inference.py:227-229 computes it in fp32, then casts)
   float dout_b = 0.f;
   std::vector<DacBlock> dblocks;
   int pca_kpad = 0;
+  static constexpr bool DAC_BF16 = sizeof(T) == 2;
+  static int cpad(int c) { return DAC_BF16 ? (int)rup(c, 64) : c; }
 
-  int fpack(const std::string& name, float** dst, long rows_pad, int rows, int cols, long cols_pad, hipStream_t st, int swh = -1, float** existing = nullptr) {
+  // elements of zero padding in front of the decode buffers.  The fp32 encode path shares b_dacA/B/C and keeps ITS zero rows in front of byte
+  // 4 * 64 * max(decoder_dim, 4 C, 16 enc_dim) (dac_encode); the bf16 decoder starts at that same byte, so neither path writes into the other's padding.
+  long dac_padf() const {
+    const long base = 64L * std::max(cfg.dac_decoder_dim, 4 * cfg.dac_latent_dim);
+    if (!DAC_BF16) return base;
+    return 2 * std::max(base, 64L * 16 * cfg.dac_enc_dim);
+  }
+  template <typename X>
+  int fpack(const std::string& name, X** dst, long rows_pad, int rows, int cols, long cols_pad, hipStream_t st, int swh = -1, X** existing = nullptr) {
     const RawTensor* r = find(name);
     if (!r) return fail("missing tensor: " + name);
     if (r->numel != (long)rows * cols) return fail("shape mismatch for " + name + " (" + std::to_string(r->numel) + " vs " + std::to_string((long)rows * cols) + ")");
-    if (!existing) { CK(alloc_zero((void**)dst, (size_t)rows_pad * cols_pad * sizeof(float))); } else { *dst = *existing; }
-    CK(launch_pack_rows(r->d, r->dtype, cols, *dst, ECHO_F32, cols_pad, rows, cols, 0, swh, st));
+    if (!existing) { CK(alloc_zero((void**)dst, (size_t)rows_pad * cols_pad * sizeof(X))); } else { *dst = *existing; }
+    CK(launch_pack_rows(r->d, r->dtype, cols, *dst, DT<X>::code, cols_pad, rows, cols, 0, swh, st));
     return ECHO_OK;
   }
-  int fvec(const std::string& name, float** dst, int n, hipStream_t st) { return fpack(name, dst, 1, 1, n, rup(n, 4), st); }
+  template <typename X>
+  int fvec(const std::string& name, X** dst, int n, hipStream_t st) { return fpack<X>(name, dst, 1, 1, n, rup(n, 8), st); }
 
   int finalize_dac(hipStream_t st) override {
     const int C = cfg.dac_latent_dim, nh = cfg.dac_post_heads, hd = cfg.dac_post_head_dim, ff = cfg.dac_post_ffn;
     if (C % 32 || C > 1024 || (nh * hd) % 32 || ff % 64 || hd != 64 || C != nh * hd) return fail("unsupported DAC sizes");
+    if (DAC_BF16 && (C % 64 || cfg.dac_decoder_dim % 64)) return fail("the bf16 DAC needs latent_dim and decoder_dim to be multiples of 64");
     const std::string pm = "quantizer.post_module";
     for (int i = 0; i < cfg.dac_post_layers; ++i) {
       const std::string lp = pm + ".layers." + std::to_string(i);
-      DacLayer L{};
+      DacLayerT<T> L{};
       CKI(fpack(lp + ".attention.wqkv.weight", &L.wqkv, rup(3 * nh * hd, 128), 3 * nh * hd, C, C, st));
       CKI(fpack(lp + ".attention.wo.weight", &L.wo, rup(C, 128), C, nh * hd, nh * hd, st));
       CKI(fpack(lp + ".feed_forward.w1.weight", &L.w13, rup(2 * ff, 128), ff, C, C, st, 0));
@@ -1453,7 +1473,7 @@ struct Engine : EngineBase {
     CKI(fvec(pm + ".norm.weight", &dpost_norm, C, st));
     for (int i = 0; i < cfg.dac_n_up; ++i) {
       const std::string up = "quantizer.upsample." + std::to_string(i);
-      DacUp U{};
+      DacUpT<T> U{};
       U.f = cfg.dac_up_factors[cfg.dac_n_up - 1 - i];
       CKI(fpack(up + ".0.conv.weight", &U.w, rup(U.f * C, 128), U.f * C, C, C, st));           // (f*Co, Ci), GEMM form
       CKI(fvec(up + ".0.conv.bias", &U.b, C, st));
@@ -1469,15 +1489,16 @@ struct Engine : EngineBase {
       dups.push_back(U);
     }
     const std::string dm = "decoder.model";
-    int ch = cfg.dac_decoder_dim;
-    if (ch % 32) return fail("decoder_dim must be a multiple of 32");
+    const int ch_raw = cfg.dac_decoder_dim;
+    if (ch_raw % 32) return fail("decoder_dim must be a multiple of 32");
+    const int ch = cpad(ch_raw);
     CKI(fpack(dm + ".0.conv.weight", &dconv0_w, rup(ch, 128), ch, 7 * C, 7 * C, st));          // (Co, 7*Ci)
     CKI(fvec(dm + ".0.conv.bias", &dconv0_b, ch, st));
     const int nr = cfg.dac_n_rates;
     for (int i = 0; i < nr; ++i) {
       DacBlock Bk{};
-      Bk.ci = ch >> i; Bk.co = ch >> (i + 1); Bk.r = cfg.dac_rates[i];
-      if (Bk.co % 32) return fail("decoder channel counts must be multiples of 32");
+      if ((ch_raw >> (i + 1)) % 32) return fail("decoder channel counts must be multiples of 32");
+      Bk.ci = cpad(ch_raw >> i); Bk.co = cpad(ch_raw >> (i + 1)); Bk.r = cfg.dac_rates[i];
       const std::string bp = dm + "." + std::to_string(i + 1) + ".block";
       CKI(fvec(bp + ".0.alpha", &Bk.alpha, Bk.ci, st));
       CKI(fpack(bp + ".1.conv.weight", &Bk.wt, rup(Bk.r * Bk.co, 128), Bk.r * Bk.co, 2 * Bk.ci, 2 * Bk.ci, st));  // (r*Co, 2*Ci)
@@ -1494,7 +1515,7 @@ struct Engine : EngineBase {
       }
       dblocks.push_back(Bk);
     }
-    const int cl = ch >> nr;
+    const int cl = cpad(ch_raw >> nr);
     CKI(fvec(dm + "." + std::to_string(nr + 1) + ".alpha", &dfinal_alpha, cl, st));
     CKI(fpack(dm + "." + std::to_string(nr + 2) + ".conv.weight", &dout_w, 7, 7, cl, cl, st));    // (7, C)
     {
@@ -1509,6 +1530,7 @@ struct Engine : EngineBase {
     CK(alloc_zero((void**)&pca_w, (size_t)rup(C, 128) * pca_kpad * sizeof(float)));
     CK(alloc_zero((void**)&pca_b, (size_t)rup(C, 4) * sizeof(float)));
     // the decoder's conv weights in the SPLIT3 kernels' pre-split format (gemm.hip, GemmArgs.w_presplit): they are GEMM W operands only
+    if constexpr (!DAC_BF16) {
     if (dac_split3) {
       CK(launch_presplit_w(dconv0_w, rup(cfg.dac_decoder_dim, 128), 7L * C, st));
       for (auto& Bk : dblocks) {
@@ -1518,6 +1540,7 @@ struct Engine : EngineBase {
           CK(launch_presplit_w(ru.w1, rup(Bk.co, 128), Bk.co, st));
         }
       }
+    }
     }
     CK(hipStreamSynchronize(st));
     drop_raw({"quantizer.", "decoder."});
@@ -1531,16 +1554,32 @@ struct Engine : EngineBase {
   // CPU restatement, three orders inside the 1e-4 waveform tolerance; sinf() was ~38 VALU instructions per output element of every conv
   bool dac_fast_sin = getenv("ECHO_DAC_FAST_SIN") ? atoi(getenv("ECHO_DAC_FAST_SIN")) != 0 : true;
   DevBuf b_sink;      // GemmArgs.sink: where the branch-free conv tails send the stores of their idle threads
+  // X = float: split-3 (or exact fp32) kernels; X = bf16_t: the native bf16 tile kernels (ECHO_DAC_EXACT_FP32 has no meaning there)
+  template <typename X>
   int frun(const GemmArgs& g_in, hipStream_t st) {
     GemmArgs g = g_in;
-    g.split3 = dac_split3 ? 1 : 0;
+    g.split3 = sizeof(X) == 4 && dac_split3 ? 1 : 0;
+    if (sizeof(X) == 2) g.w_presplit = 0;
     if (!b_sink.p) CK(b_sink.reserve(262144));
     g.sink = b_sink.p;
     g.snake_fast = dac_fast_sin ? 1 : 0;
-    CKI(plan_gemm<float>(g, st));
-    return run_planned<float>(g, st, false);
+    if constexpr (sizeof(X) == 2) {
+      // bf16 DAC: a fixed rule, no plan table, no split-K and no ping-pong kernel.  Every tile configuration of gemm_nt_kernel walks K in the
+      // same order on the same MFMA, so each output keeps ONE summation chain whatever M is: a batched front (M = B * T), a single decode and
+      // a streaming tail give the same bits for the same rows.  That matters more in bf16 than in fp32: a difference in the last fp32 bit of
+      // an accumulator flips bf16 roundings, and ~100 rounding layers amplify such flips to the size of the bf16 error itself (measured: 1.2 %
+      // of the signal between a 3 x 136-frame batch and its single decodes with the shared plan rule's M-dependent split-K).
+      const bool big = (long)g.M * g.Npad >= 256L * 256 * 64;
+      // N = 128 (the padded last block, 1.3 M rows at 640 frames): a 256-column tile would spend half its MFMAs on clamped weight rows
+      g.cfg = !big ? 0 : g.N % 192 == 0 && g.N % 256 != 0 ? 8 : g.N % 96 == 0 && g.N % 128 != 0 ? 9 : g.N % 256 > 0 && g.N % 256 <= 128 ? 3 : 2;
+      g.ksplit = 1;
+    } else {
+      CKI(plan_gemm<X>(g, st));
+    }
+    return run_planned<X>(g, st, false);
   }
-  static GemmArgs FG(const float* A, long lda, const float* W, long ldw, float* C, long ldc, long M, int N, int K) {
+  template <typename X>
+  static GemmArgs FG(const X* A, long lda, const X* W, long ldw, X* C, long ldc, long M, int N, int K) {
     GemmArgs g;
     gemm_args_init(&g);
     g.A = A; g.lda = lda; g.W = W; g.ldw = ldw; g.C = C; g.ldc = ldc; g.M = (int)M; g.N = N; g.K = K;
@@ -1579,44 +1618,48 @@ struct Engine : EngineBase {
   // and Tn*C floats).  autoencoder.py:786-802, 590-626, 663-717.  The final RMSNorm is applied by the caller.
   // `B` items of `Tn` frames each, stacked as B * Tn rows: every row-wise GEMM / norm sees all rows at once (M = 15360 instead of 24 x 640
   // for a bench call), the attention is per (item, head) through the two-level batch strides of the GEMM descriptor
-  int dac_transformer(std::vector<DacLayer>& layers, float* x, int Tn, int C, int nh, int hd, int ff, int window, float* xn_buf,
-                      float* ao_buf, hipStream_t st, int B = 1) {
+  // X = bf16_t (decode path of a bf16 context): same schedule on bf16 rows; scores and probabilities are bf16 too (the key axis is padded to the
+  // bf16 K step), every GEMM accumulates in fp32 and rounds where the reference materialises a tensor.
+  template <typename X>
+  int dac_transformer(std::vector<DacLayerT<X>>& layers, X* x, int Tn, int C, int nh, int hd, int ff, int window, X* xn_buf,
+                      X* ao_buf, hipStream_t st, int B = 1) {
     if (!ae_rope || Tn > ae_rope_npos) return fail("ae rope table missing or too short");
     if (hd != 64 || C != nh * hd || ff % 64) return fail("unsupported transformer sizes");
     const int R = B * Tn;
     const int Tp = (int)rup(R, 128);
     const long ldq = 3L * nh * hd;
-    const int Tk = (int)rup(Tn, 32);
+    const int Tk = (int)rup(Tn, 128 / (int)sizeof(X));
     const int vld = (int)rup(Tn, 64);
     const long vt_item = (long)nh * hd * vld;
-    CK(b_dq.reserve((size_t)(Tp + 128) * ldq * sizeof(float)));
-    CK(b_dscore.reserve((size_t)B * nh * Tn * Tk * sizeof(float)));
-    CK(b_dvt.reserve((size_t)(B * vt_item + (long)hd * vld + 128L * vld) * sizeof(float)));
-    float *xn = xn_buf, *qkv = b_dq.as<float>(), *sc = b_dscore.as<float>(), *vt = b_dvt.as<float>(), *ao = ao_buf, *hh = xn_buf + (long)Tp * C;
+    CK(b_dq.reserve((size_t)(Tp + 128) * ldq * sizeof(X)));
+    CK(b_dscore.reserve((size_t)B * nh * Tn * Tk * sizeof(X)));
+    CK(b_dvt.reserve((size_t)(B * vt_item + (long)hd * vld + 128L * vld) * sizeof(X)));
+    X *xn = xn_buf, *qkv = b_dq.as<X>(), *sc = b_dscore.as<X>(), *vt = b_dvt.as<X>(), *ao = ao_buf, *hh = xn_buf + (long)Tp * C;
     for (auto& L : layers) {
-      CK(launch_norm<float>(NORM_AE_RMS, x, C, xn, C, R, C, cfg.dac_norm_eps, L.an, nullptr, st));
-      CKI(frun(FG(xn, C, L.wqkv, C, qkv, ldq, R, 3 * nh * hd, C), st));
+      CK(launch_norm<X>(NORM_AE_RMS, x, C, xn, C, R, C, cfg.dac_norm_eps, L.an, nullptr, st));
+      CKI(frun<X>(FG(xn, C, L.wqkv, C, qkv, ldq, R, 3 * nh * hd, C), st));
       CK(launch_ae_rope(qkv, ldq, R, Tn, nh, hd, ae_rope, st));
       CK(launch_ae_rope(qkv + nh * hd, ldq, R, Tn, nh, hd, ae_rope, st));
-      CK(launch_transpose_heads<float>(qkv + 2 * nh * hd, ldq, vt, vld, vt_item, B, Tn, nh, hd, st));
+      CK(launch_transpose_heads<X>(qkv + 2 * nh * hd, ldq, vt, vld, vt_item, B, Tn, nh, hd, st));
       {
         GemmArgs g = FG(qkv, ldq, qkv + nh * hd, ldq, sc, Tk, Tn, Tk, hd);
         g.nbatch = B * nh; g.nbi = nh;
         g.a_bo = (long)Tn * ldq; g.a_bi = hd; g.w_bo = (long)Tn * ldq; g.w_bi = hd; g.c_bo = (long)nh * Tn * Tk; g.c_bi = (long)Tn * Tk;
         g.acc_scale = 1.0f / sqrtf((float)hd);
-        CKI(frun(g, st));
+        CKI(frun<X>(g, st));
       }
-      CK(launch_softmax_f32(sc, Tk, Tn, B * nh, Tn, Tk, nullptr, 0, 1, 1, window, st));
+      if constexpr (sizeof(X) == 2) CK(launch_softmax_window_bf16(sc, Tk, Tn, B * nh, Tn, Tk, window, st));
+      else CK(launch_softmax_f32(sc, Tk, Tn, B * nh, Tn, Tk, nullptr, 0, 1, 1, window, st));
       {
         GemmArgs g = FG(sc, Tk, vt, vld, ao, C, Tn, hd, Tk);
         g.nbatch = B * nh; g.nbi = nh;
         g.a_bo = (long)nh * Tn * Tk; g.a_bi = (long)Tn * Tk; g.w_bo = vt_item; g.w_bi = (long)hd * vld; g.c_bo = (long)Tn * C; g.c_bi = hd;
-        CKI(frun(g, st));
+        CKI(frun<X>(g, st));
       }
-      { GemmArgs g = FG(ao, C, L.wo, nh * hd, x, C, R, C, nh * hd); g.colscale = L.ga; g.res = x; g.ldres = C; CKI(frun(g, st)); }
-      CK(launch_norm<float>(NORM_AE_RMS, x, C, xn, C, R, C, cfg.dac_norm_eps, L.fn, nullptr, st));
-      { GemmArgs g = FG(xn, C, L.w13, C, hh, ff, R, 2 * ff, C); g.swiglu = 1; CKI(frun(g, st)); }
-      { GemmArgs g = FG(hh, ff, L.w2, ff, x, C, R, C, ff); g.colscale = L.gf; g.res = x; g.ldres = C; CKI(frun(g, st)); }
+      { GemmArgs g = FG(ao, C, L.wo, nh * hd, x, C, R, C, nh * hd); g.colscale = L.ga; g.res = x; g.ldres = C; CKI(frun<X>(g, st)); }
+      CK(launch_norm<X>(NORM_AE_RMS, x, C, xn, C, R, C, cfg.dac_norm_eps, L.fn, nullptr, st));
+      { GemmArgs g = FG(xn, C, L.w13, C, hh, ff, R, 2 * ff, C); g.swiglu = 1; CKI(frun<X>(g, st)); }
+      { GemmArgs g = FG(hh, ff, L.w2, ff, x, C, R, C, ff); g.colscale = L.gf; g.res = x; g.ldres = C; CKI(frun<X>(g, st)); }
     }
     return ECHO_OK;
   }
@@ -1782,13 +1825,13 @@ struct Engine : EngineBase {
           GemmArgs g = FG(S, ci, ru.w7, 7L * ci, U, ci, rows, ci, ci);
           g.taps = 7; g.tap_base = -6 * dil[j]; g.tap_shift = dil[j]; g.bias = ru.b7;
           g.store_main = 0; g.C2 = U; g.snake_alpha = ru.a1;
-          CKI(frun(g, st));
+          CKI(frun<float>(g, st));
         }
         {   // conv k1 + residual; second output = Snake with the next consumer's alpha
           GemmArgs g = FG(U, ci, ru.w1, ci, Y, ci, rows, ci, ci);
           g.bias = ru.b1; g.res = Y; g.ldres = ci;
           g.store_main = j < 2 ? 1 : 0; g.C2 = S; g.snake_alpha = j < 2 ? Bk.ru[j + 1].a0 : Bk.alpha;
-          CKI(frun(g, st));
+          CKI(frun<float>(g, st));
         }
       }
       {   // conv k = 2r, stride r, ci -> co: rows of r*ci, taps {row j-1, row j}
@@ -1796,7 +1839,7 @@ struct Engine : EngineBase {
         GemmArgs g = FG(S, (long)r * ci, Bk.wc, 2L * r * ci, Y, co, rows2, co, r * ci);
         g.taps = 2; g.tap_base = -1; g.tap_shift = 1; g.bias = Bk.bc;
         if (bi + 1 < eblocks.size() && Bk.tl.empty()) { g.C2 = U; g.snake_alpha = eblocks[bi + 1].ru[0].a0; }
-        CKI(frun(g, st));
+        CKI(frun<float>(g, st));
         rows = rows2;
         if (g.C2) std::swap(S, U);
       }
@@ -1812,16 +1855,16 @@ struct Engine : EngineBase {
     {   // conv k3 -> latent_dim
       GemmArgs g = FG(S, chL, econvL_w, 3L * chL, Y, C, rows, C, chL);
       g.taps = 3; g.tap_base = -2; g.tap_shift = 1; g.bias = econvL_b;
-      CKI(frun(g, st));
+      CKI(frun<float>(g, st));
     }
     // ---- quantizer.downsample: [conv k = f stride f ; ConvNeXt] (autoencoder.py:418-426, 360-373)
     for (auto& D : ddowns) {
       const long rows2 = rows / D.f;
-      { GemmArgs g = FG(Y, (long)D.f * C, D.w, (long)D.f * C, S, C, rows2, C, D.f * C); g.bias = D.b; CKI(frun(g, st)); }
+      { GemmArgs g = FG(Y, (long)D.f * C, D.w, (long)D.f * C, S, C, rows2, C, D.f * C); g.bias = D.b; CKI(frun<float>(g, st)); }
       rows = rows2;
       CK(launch_dwconv_ln(S, C, U, C, (int)rows, (int)rows, C, D.dw, D.db, D.lnw, D.lnb, 1e-6f, st));
-      { GemmArgs g = FG(U, C, D.p1w, C, Y, 4L * C, rows, 4 * C, C); g.bias = D.p1b; g.act = 2; CKI(frun(g, st)); }
-      { GemmArgs g = FG(Y, 4L * C, D.p2w, 4L * C, S, C, rows, C, 4 * C); g.bias = D.p2b; g.colscale = D.gamma; g.res = S; g.ldres = C; CKI(frun(g, st)); }
+      { GemmArgs g = FG(U, C, D.p1w, C, Y, 4L * C, rows, 4 * C, C); g.bias = D.p1b; g.act = 2; CKI(frun<float>(g, st)); }
+      { GemmArgs g = FG(Y, 4L * C, D.p2w, 4L * C, S, C, rows, C, 4 * C); g.bias = D.p2b; g.colscale = D.gamma; g.res = S; g.ldres = C; CKI(frun<float>(g, st)); }
       std::swap(Y, S);
     }
     // ---- pre_module
@@ -1839,18 +1882,18 @@ struct Engine : EngineBase {
     int* idx = b_vq_idx.as<int>();
     for (int q = 0; q < nq; ++q) {
       VQ& v = vqs[q];
-      { GemmArgs g = FG(Y, C, v.in_w, C, e8, cd, Tn, cd, C); g.bias = v.in_b; CKI(frun(g, st)); }
+      { GemmArgs g = FG(Y, C, v.in_w, C, e8, cd, Tn, cd, C); g.bias = v.in_b; CKI(frun<float>(g, st)); }
       CK(launch_vq_argmax(e8, cd, Tn, v.cbn, v.cb, v.size, idx + (long)q * Tn, zst, 32, gath + q * cd, fc_kpad, st));
-      { GemmArgs g = FG(zst, 32, v.out_w, 32, Y, C, Tn, C, 32); g.acc_scale = -1.0f; g.bias = v.out_nb; g.res = Y; g.ldres = C; CKI(frun(g, st)); }
+      { GemmArgs g = FG(zst, 32, v.out_w, 32, Y, C, Tn, C, 32); g.acc_scale = -1.0f; g.bias = v.out_nb; g.res = Y; g.ldres = C; CKI(frun<float>(g, st)); }
     }
     // ---- encode_zq: sum over quantizers of out_proj(codebook[code]) as one GEMM over the gathered code vectors
-    { GemmArgs g = FG(gath, fc_kpad, fc_w, fc_kpad, S, C, Tn, C, fc_kpad); g.bias = fc_b; CKI(frun(g, st)); }
+    { GemmArgs g = FG(gath, fc_kpad, fc_w, fc_kpad, S, C, Tn, C, fc_kpad); g.bias = fc_b; CKI(frun<float>(g, st)); }
     if (zq_out) CK(hipMemcpyAsync(zq_out, S, (size_t)Tn * C * sizeof(float), hipMemcpyDeviceToDevice, st));
     if (codes_out) CK(hipMemcpyAsync(codes_out, idx, (size_t)nq * Tn * sizeof(int), hipMemcpyDeviceToDevice, st));
     if (lat_out) {   // ((z_q - mean) @ P^T) * scale, mean folded into the bias (inference.py:221-223)
       GemmArgs g = FG(S, C, pcae_w, C, lat_out, cfg.latent_size, Tn, cfg.latent_size, C);
       g.bias = pcae_b; g.colscale = pcae_scale;
-      CKI(frun(g, st));
+      CKI(frun<float>(g, st));
     }
     return ECHO_OK;
   }
@@ -1862,8 +1905,22 @@ struct Engine : EngineBase {
   // dac_run(..., front = that pointer) runs the decoder convolutions on them.
   DevBuf b_dfx, b_dfs, b_dfu, b_dfn;
   float dac_front_ms = 0.f;         // profiling: the last batched front's time (dac_decode_batch divides it over its items)
-  float* dac_front_out = nullptr;   // item b's upsampled rows: dac_front_out + b * dac_front_item_rows * C
+  T* dac_front_out = nullptr;       // item b's upsampled rows: dac_front_out + b * dac_front_item_rows * C
   long dac_front_item_rows = 0;
+  // PCA inverse (inference.py:228) for R rows: z = (latent / scale) @ components + mean, in fp32 in both precisions; the bf16 decoder rounds the
+  // result once (the reference's `.to(fish_ae.dtype)`, inference.py:229).  b_dmisc: [Rp x pca_kpad operand | bf16 only: Rp x C fp32 result].
+  int dac_pca_inverse(const float* lat, long R, long Rp, float latent_scale, T* x, hipStream_t st) {
+    const int C = cfg.dac_latent_dim;
+    float* prep = b_dmisc.as<float>();
+    CK(launch_pca_prep(lat, prep, pca_kpad, R, cfg.latent_size, pca_kpad, latent_scale, st));
+    float* z;
+    if constexpr (DAC_BF16) z = prep + Rp * pca_kpad; else z = x;
+    GemmArgs g = FG(prep, pca_kpad, pca_w, pca_kpad, z, C, R, C, pca_kpad);
+    g.bias = pca_b;
+    CKI(frun<float>(g, st));
+    if constexpr (DAC_BF16) CK(launch_convert_from_f32<T>(z, C, x, C, (int)R, C, C, st));
+    return ECHO_OK;
+  }
   int dac_front_batch(const float* lat, int B, int Tn, float latent_scale, hipStream_t st) {
     if (!dac_ready) return fail("echo_finalize_dac was not called");
     if (!pca_set) return fail("echo_set_pca was not called");
@@ -1872,35 +1929,30 @@ struct Engine : EngineBase {
     long upf = 1;
     for (int i = 0; i < cfg.dac_n_up; ++i) upf *= cfg.dac_up_factors[i];
     const long Rup = rup(R * upf, 128) + 128;       // rows after quantizer.upsample
-    CK(b_dfx.reserve((size_t)Rup * C * sizeof(float)));
-    CK(b_dfs.reserve((size_t)std::max((Tp + 128) * (long)(C + ff), Rup * 4L * C) * sizeof(float)));
-    CK(b_dfu.reserve((size_t)(Tp + 128) * C * sizeof(float)));
-    CK(b_dfn.reserve((size_t)Rup * C * sizeof(float)));
-    CK(b_dmisc.reserve((size_t)Tp * pca_kpad * sizeof(float)));
+    CK(b_dfx.reserve((size_t)Rup * C * sizeof(T)));
+    CK(b_dfs.reserve((size_t)std::max((Tp + 128) * (long)(C + ff), Rup * 4L * C) * sizeof(T)));
+    CK(b_dfu.reserve((size_t)(Tp + 128) * C * sizeof(T)));
+    CK(b_dfn.reserve((size_t)Rup * C * sizeof(T)));
+    CK(b_dmisc.reserve((size_t)Tp * (pca_kpad + (DAC_BF16 ? C : 0)) * sizeof(float)));
     if (profiling) {
       for (auto& e : ev) if (!e) CK(hipEventCreate(&e));
       CK(hipEventRecord(ev[4], st));
     }
-    float* x = b_dfx.as<float>();
-    CK(launch_pca_prep(lat, b_dmisc.as<float>(), pca_kpad, R, cfg.latent_size, pca_kpad, latent_scale, st));
-    {
-      GemmArgs g = FG(b_dmisc.as<float>(), pca_kpad, pca_w, pca_kpad, x, C, R, C, pca_kpad);
-      g.bias = pca_b;
-      CKI(frun(g, st));
-    }
-    CKI(dac_transformer(dpost, x, Tn, C, nh, hd, ff, cfg.dac_post_window, b_dfs.as<float>(), b_dfu.as<float>(), st, B));
-    CK(launch_norm<float>(NORM_AE_RMS, x, C, b_dfn.as<float>(), C, (int)R, C, cfg.dac_norm_eps, dpost_norm, nullptr, st));
+    T* x = b_dfx.as<T>();
+    CKI(dac_pca_inverse(lat, R, Tp, latent_scale, x, st));
+    CKI(dac_transformer<T>(dpost, x, Tn, C, nh, hd, ff, cfg.dac_post_window, b_dfs.as<T>(), b_dfu.as<T>(), st, B));
+    CK(launch_norm<T>(NORM_AE_RMS, x, C, b_dfn.as<T>(), C, (int)R, C, cfg.dac_norm_eps, dpost_norm, nullptr, st));
     // quantizer.upsample on the stacked rows as well (autoencoder.py:427-435, 360-373): the ConvTranspose is a 1-tap GEMM, the ConvNeXt's
     // causal depthwise conv restarts its padding per item (dwconv_ln_kernel: position = row % rows_per_item), the rest is row-wise
     {
-      float *cur = b_dfn.as<float>(), *other = x, *third = b_dfs.as<float>();
+      T *cur = b_dfn.as<T>(), *other = x, *third = b_dfs.as<T>();
       long rows = R, per_item = Tn;
       for (auto& U : dups) {
-        { GemmArgs g = FG(cur, C, U.w, C, other, (long)U.f * C, rows, U.f * C, C); g.bias = U.b; g.vec_mod = C; CKI(frun(g, st)); }
+        { GemmArgs g = FG(cur, C, U.w, C, other, (long)U.f * C, rows, U.f * C, C); g.bias = U.b; g.vec_mod = C; CKI(frun<T>(g, st)); }
         rows *= U.f; per_item *= U.f;
         CK(launch_dwconv_ln(other, C, cur, C, (int)rows, (int)per_item, C, U.dw, U.db, U.lnw, U.lnb, 1e-6f, st));
-        { GemmArgs g = FG(cur, C, U.p1w, C, third, 4L * C, rows, 4 * C, C); g.bias = U.p1b; g.act = 2; CKI(frun(g, st)); }
-        { GemmArgs g = FG(third, 4L * C, U.p2w, 4L * C, other, C, rows, C, 4 * C); g.bias = U.p2b; g.colscale = U.gamma; g.res = other; g.ldres = C; CKI(frun(g, st)); }
+        { GemmArgs g = FG(cur, C, U.p1w, C, third, 4L * C, rows, 4 * C, C); g.bias = U.p1b; g.act = 2; CKI(frun<T>(g, st)); }
+        { GemmArgs g = FG(third, 4L * C, U.p2w, 4L * C, other, C, rows, C, 4 * C); g.bias = U.p2b; g.colscale = U.gamma; g.res = other; g.ldres = C; CKI(frun<T>(g, st)); }
         std::swap(cur, other);
       }
       dac_front_out = cur; dac_front_item_rows = per_item;
@@ -1927,7 +1979,7 @@ struct Engine : EngineBase {
     return ECHO_OK;
   }
 
-  int dac_run(const float* lat, const float* zq, int Tn, float latent_scale, float* wav, hipStream_t st, int f0 = 0, const float* front = nullptr) {
+  int dac_run(const float* lat, const float* zq, int Tn, float latent_scale, float* wav, hipStream_t st, int f0 = 0, const T* front = nullptr) {
     if (!dac_ready) return fail("echo_finalize_dac was not called");
     if (!ae_rope || Tn > ae_rope_npos) return fail("ae rope table missing or too short");
     const int C = cfg.dac_latent_dim, nh = cfg.dac_post_heads, hd = cfg.dac_post_head_dim, ff = cfg.dac_post_ffn;
@@ -1941,10 +1993,10 @@ struct Engine : EngineBase {
       long rows = (long)Tn * upf;
       for (auto& b : dblocks) { rows *= b.r; maxel = std::max(maxel, rows * b.co); }
     }
-    const long PADF = 64L * std::max(cfg.dac_decoder_dim, 4 * C);   // zero rows in front of every buffer (causal left padding)
-    const size_t bytes = (size_t)(maxel + PADF + 128L * 4 * C) * sizeof(float);
+    const long PADF = dac_padf();   // zero rows in front of every buffer (causal left padding)
+    const size_t bytes = (size_t)(maxel + PADF + 128L * 4 * C) * sizeof(T);
     CK(b_dacA.reserve(bytes)); CK(b_dacB.reserve(bytes)); CK(b_dacC.reserve(bytes));
-    float *bufY = b_dacA.as<float>() + PADF, *bufS = b_dacB.as<float>() + PADF, *bufU = b_dacC.as<float>() + PADF;
+    T *bufY = b_dacA.as<T>() + PADF, *bufS = b_dacB.as<T>() + PADF, *bufU = b_dacC.as<T>() + PADF;
     if (profiling) {
       for (auto& e : ev) if (!e) CK(hipEventCreate(&e));
       gemm_events_used = 0;
@@ -1952,51 +2004,50 @@ struct Engine : EngineBase {
     }
     // ---- PCA inverse (inference.py:228): z = (latent / scale) @ components + mean
     const int Tp = (int)rup(Tn, 128);
-    CK(b_dmisc.reserve((size_t)Tp * pca_kpad * sizeof(float)));
-    float* x = bufY;
+    CK(b_dmisc.reserve((size_t)Tp * (pca_kpad + (DAC_BF16 ? C : 0)) * sizeof(float)));
+    T* x = bufY;
     if (front) {
       // the front (incl. quantizer.upsample) already ran for the whole batch (dac_front_batch): this item's rows go to its own buffer,
       // whose zero rows in front are the causal padding of the first decoder conv
-      CK(hipMemcpyAsync(bufS, front, (size_t)Tn * upf * C * sizeof(float), hipMemcpyDeviceToDevice, st));
+      CK(hipMemcpyAsync(bufS, front, (size_t)Tn * upf * C * sizeof(T), hipMemcpyDeviceToDevice, st));
     } else {
     if (lat) {
-      CK(launch_pca_prep(lat, b_dmisc.as<float>(), pca_kpad, Tn, cfg.latent_size, pca_kpad, latent_scale, st));
-      GemmArgs g = FG(b_dmisc.as<float>(), pca_kpad, pca_w, pca_kpad, x, C, Tn, C, pca_kpad);
-      g.bias = pca_b;
-      CKI(frun(g, st));
+      CKI(dac_pca_inverse(lat, Tn, Tp, latent_scale, x, st));
+    } else if constexpr (DAC_BF16) {
+      CK(launch_convert_from_f32<T>(zq, C, x, C, Tn, C, C, st));      // z_q.to(fish_ae.dtype) (autoencoder.py:1128-1132 on a bf16 module)
     } else {
       CK(hipMemcpyAsync(x, zq, (size_t)Tn * C * sizeof(float), hipMemcpyDeviceToDevice, st));
     }
     // ---- post_module: window-limited causal transformer (autoencoder.py:786-802)
-    CKI(dac_transformer(dpost, x, Tn, C, nh, hd, ff, cfg.dac_post_window, bufS, bufU, st));
-    CK(launch_norm<float>(NORM_AE_RMS, x, C, bufS, C, Tn, C, cfg.dac_norm_eps, dpost_norm, nullptr, st));
+    CKI(dac_transformer<T>(dpost, x, Tn, C, nh, hd, ff, cfg.dac_post_window, bufS, bufU, st));
+    CK(launch_norm<T>(NORM_AE_RMS, x, C, bufS, C, Tn, C, cfg.dac_norm_eps, dpost_norm, nullptr, st));
     }
     // ---- quantizer.upsample: [ConvT k=f s=f ; ConvNeXt] (autoencoder.py:427-435, 360-373)
     // f0 > 0: only frames f0.. go through the convolutions; the first conv's causal taps then read the real frames in front
     // of f0 (still in bufS), every later one the zero rows in front of its buffer
-    float* cur = bufS + (long)f0 * C;      // (rows, C)
-    float* other = bufY;
-    float* third = bufU;
+    T* cur = bufS + (long)f0 * C;      // (rows, C)
+    T* other = bufY;
+    T* third = bufU;
     long rows = front ? (long)Tn * upf : Tn - f0;
     if (!front)
     for (auto& U : dups) {
-      { GemmArgs g = FG(cur, C, U.w, C, other, (long)U.f * C, rows, U.f * C, C); g.bias = U.b; g.vec_mod = C; CKI(frun(g, st)); }
+      { GemmArgs g = FG(cur, C, U.w, C, other, (long)U.f * C, rows, U.f * C, C); g.bias = U.b; g.vec_mod = C; CKI(frun<T>(g, st)); }
       rows *= U.f;
       CK(launch_dwconv_ln(other, C, cur, C, (int)rows, (int)rows, C, U.dw, U.db, U.lnw, U.lnb, 1e-6f, st));
-      { GemmArgs g = FG(cur, C, U.p1w, C, third, 4L * C, rows, 4 * C, C); g.bias = U.p1b; g.act = 2; CKI(frun(g, st)); }
-      { GemmArgs g = FG(third, 4L * C, U.p2w, 4L * C, other, C, rows, C, 4 * C); g.bias = U.p2b; g.colscale = U.gamma; g.res = other; g.ldres = C; CKI(frun(g, st)); }
+      { GemmArgs g = FG(cur, C, U.p1w, C, third, 4L * C, rows, 4 * C, C); g.bias = U.p1b; g.act = 2; CKI(frun<T>(g, st)); }
+      { GemmArgs g = FG(third, 4L * C, U.p2w, 4L * C, other, C, rows, C, 4 * C); g.bias = U.p2b; g.colscale = U.gamma; g.res = other; g.ldres = C; CKI(frun<T>(g, st)); }
       std::swap(cur, other);
     }
     // ---- decoder (autoencoder.py:971-998): every conv is a taps-GEMM on channels-last rows
-    float *Y = other, *S = third, *Uu = nullptr;
+    T *Y = other, *S = third, *Uu = nullptr;
     {
       // conv k7 C -> ch, epilogue writes only snake_{block1}(y)
-      const int ch = cfg.dac_decoder_dim;
+      const int ch = cpad(cfg.dac_decoder_dim);
       GemmArgs g = FG(cur, C, dconv0_w, 7L * C, Y, ch, rows, ch, C);
-      g.w_presplit = dac_split3;
+      g.w_presplit = !DAC_BF16 && dac_split3;
       g.taps = 7; g.tap_base = -6; g.tap_shift = 1; g.bias = dconv0_b;
       g.store_main = 0; g.C2 = S; g.snake_alpha = dblocks[0].alpha;
-      CKI(frun(g, st));
+      CKI(frun<T>(g, st));
       Uu = cur;
     }
     for (size_t bi = 0; bi < dblocks.size(); ++bi) {
@@ -2004,10 +2055,10 @@ struct Engine : EngineBase {
       {
         // ConvTranspose k=2r s=r as a 2-tap GEMM with N = r*Co; rows of C are r consecutive output steps
         GemmArgs g = FG(S, Bk.ci, Bk.wt, 2L * Bk.ci, Y, (long)Bk.r * Bk.co, rows, Bk.r * Bk.co, Bk.ci);
-        g.w_presplit = dac_split3;
+        g.w_presplit = !DAC_BF16 && dac_split3;
         g.taps = 2; g.tap_base = -1; g.tap_shift = 1; g.bias = Bk.bt; g.vec_mod = Bk.co;
         g.C2 = Uu; g.snake_alpha = Bk.ru[0].a0;
-        CKI(frun(g, st));
+        CKI(frun<T>(g, st));
         rows *= Bk.r;
         std::swap(S, Uu);   // S now holds snake_{ru0.a0}(y)
       }
@@ -2016,22 +2067,22 @@ struct Engine : EngineBase {
         DacRU& ru = Bk.ru[j];
         {
           GemmArgs g = FG(S, Bk.co, ru.w7, 7L * Bk.co, Uu, Bk.co, rows, Bk.co, Bk.co);
-          g.w_presplit = dac_split3;
+          g.w_presplit = !DAC_BF16 && dac_split3;
           g.taps = 7; g.tap_base = -6 * dil[j]; g.tap_shift = dil[j]; g.bias = ru.b7;
           g.store_main = 0; g.C2 = Uu; g.snake_alpha = ru.a1;
-          CKI(frun(g, st));
+          CKI(frun<T>(g, st));
         }
         {
-          const float* next_alpha = j < 2 ? Bk.ru[j + 1].a0 : (bi + 1 < dblocks.size() ? dblocks[bi + 1].alpha : dfinal_alpha);
+          const T* next_alpha = j < 2 ? Bk.ru[j + 1].a0 : (bi + 1 < dblocks.size() ? dblocks[bi + 1].alpha : dfinal_alpha);
           GemmArgs g = FG(Uu, Bk.co, ru.w1, Bk.co, Y, Bk.co, rows, Bk.co, Bk.co);
-          g.w_presplit = dac_split3;
+          g.w_presplit = !DAC_BF16 && dac_split3;
           g.bias = ru.b1; g.res = Y; g.ldres = Bk.co;
           g.store_main = j < 2 ? 1 : 0; g.C2 = S; g.snake_alpha = next_alpha;
-          CKI(frun(g, st));
+          CKI(frun<T>(g, st));
         }
       }
     }
-    const int cl = cfg.dac_decoder_dim >> cfg.dac_n_rates;
+    const int cl = cpad(cfg.dac_decoder_dim >> cfg.dac_n_rates);
     CK(launch_conv_out_tanh(S, cl, wav, rows, (int)rows, cl, 7, dout_w, dout_b, st));
     if (profiling) {
       CK(hipEventRecord(ev[2], st));
@@ -2253,6 +2304,14 @@ int echo_op_gemm(int dtype, const echo_gemm_desc* d, void* stream) {
   g.a_scale_const = d->a_scale_const; g.c8 = d->c8; g.c8_ld = d->c8_ld; g.c8_inv = d->c8_inv; g.qkv_gate_act = d->qkv_gate_act;
   g.qkv_mode = d->qkv_mode; g.qkv_D = d->qkv_D; g.qkv_S = d->qkv_S; g.rope_heads = d->rope_heads; g.pos0 = d->pos0; g.qk_eps = d->qk_eps;
   g.qk_w = d->qk_w; g.rope = d->rope; g.vt = d->vt; g.vt_ld = d->vt_ld; g.vt_row_stride = d->vt_row_stride;
+  if (dtype == ECHO_BF16 && g.snake_alpha && g.C2) {
+    // bf16 conv forms take the branch-free conv tails at the 96- / 192-column tiles, as in the engine: they need a sink for their idle threads' stores
+    static thread_local DevBuf sink_buf[64];
+    int dev = 0; (void)hipGetDevice(&dev);
+    DevBuf& sb = sink_buf[dev & 63];
+    if (hipError_t e = sb.reserve(262144); e != hipSuccess) return op_status(e);
+    g.sink = sb.p;
+  }
   return op_status(dtype == ECHO_BF16 ? launch_gemm_nt<bf16_t>(g, (hipStream_t)stream) : launch_gemm_nt<float>(g, (hipStream_t)stream));
 }
 int echo_op_presplit_weights(float* w, int64_t rows, int64_t ld, void* stream) {

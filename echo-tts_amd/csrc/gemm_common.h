@@ -59,10 +59,14 @@ __device__ __forceinline__ void gemm_tail_res(const GemmArgs& p, int m, int n0, 
   if (p.res) V::unpack(*(const typename V::raw*)((const T*)p.res + zo * p.res_bo + zi * p.res_bi + (long)m * p.ldres + n0), r);
 }
 
+// bf16 conv forms (snake_alpha set: the Fish S1-DAC decoder's Conv1d / ConvTranspose1d launches of a bf16 context): bias, residual and Snake are
+// evaluated in fp32 on the accumulator and each output is rounded ONCE, at its store - the same arithmetic as the branch-free conv tails of
+// gemm_epilogue (NTAIL >= 2), so that both give the same bits.  Every other bf16 launch keeps one rounding per tensor eager PyTorch materialises.
 template <typename T>
 __device__ __forceinline__ void gemm_tail_apply(const GemmArgs& p, int m, int n0, float (&y)[4], const TailCols& t, const float (&res)[4], T* C,
                                                 T* C2) {
   typedef Vec4<T> V;
+  const bool keep = Num<T>::is_bf16 && p.snake_alpha;     // fp32 tail: no intermediate rounding
   if (p.acc_scale != 1.0f) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) y[i] *= p.acc_scale;
@@ -71,8 +75,10 @@ __device__ __forceinline__ void gemm_tail_apply(const GemmArgs& p, int m, int n0
 #pragma unroll
     for (int i = 0; i < 4; ++i) y[i] += t.bias[i];
   }
+  if (!keep) {
 #pragma unroll
-  for (int i = 0; i < 4; ++i) y[i] = Num<T>::rnd(y[i]);
+    for (int i = 0; i < 4; ++i) y[i] = Num<T>::rnd(y[i]);
+  }
   if (p.div != 0.0f) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) y[i] = Num<T>::rnd(y[i] / p.div);
@@ -90,7 +96,7 @@ __device__ __forceinline__ void gemm_tail_apply(const GemmArgs& p, int m, int n0
   }
   if (p.res) {
 #pragma unroll
-    for (int i = 0; i < 4; ++i) y[i] = Num<T>::rnd(y[i] + res[i]);
+    for (int i = 0; i < 4; ++i) y[i] = keep ? y[i] + res[i] : Num<T>::rnd(y[i] + res[i]);
   }
   if (p.store_main) *(typename V::raw*)(C + (long)m * p.ldc + n0) = V::pack(y);
   if (p.snake_alpha) {

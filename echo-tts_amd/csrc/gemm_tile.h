@@ -231,10 +231,10 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& p, float* slab, in
         const f32x4 a4 = *(const f32x4*)(slab + slab_pos<CPR>(ml < 32 ? ml : 31, g_chunk) * 4);
         float y[4];
 #pragma unroll
-        for (int i = 0; i < 4; ++i) y[i] = Num<T>::rnd(Num<T>::rnd(a4[i] + tcols.bias[i]));
+        for (int i = 0; i < 4; ++i) y[i] = a4[i] + tcols.bias[i];      // fp32 throughout; bf16 outputs are rounded once, at their stores
         if constexpr (F_RES) {
 #pragma unroll
-          for (int i = 0; i < 4; ++i) y[i] = Num<T>::rnd(y[i] + rs[k][i]);
+          for (int i = 0; i < 4; ++i) y[i] = y[i] + rs[k][i];
         }
         typedef Vec4<T> V;
         if constexpr (F_MAIN) *(typename V::raw*)(ok ? (char*)(C + (long)m * p.ldc + g_n0) : sink) = V::pack(y);
@@ -518,7 +518,7 @@ hipError_t launch_cfg_tail(const GemmArgs& g, hipStream_t st);
 template <typename T, bool SW, typename CF, bool SPLIT3 = false>
 hipError_t launch_cfg(const GemmArgs& g, hipStream_t st) {
   static const bool split = getenv("ECHO_NT_TAILS") ? atoi(getenv("ECHO_NT_TAILS")) != 0 : true;      // 0: the all-tails instantiation everywhere (A/B aid)
-  if constexpr (SPLIT3 && !SW && (CF::BN == 96 || CF::BN == 192)) {      // the DAC's conv tiles: branch-free conv tails (gemm_epilogue, NTAIL >= 2)
+  if constexpr ((SPLIT3 || Num<T>::is_bf16) && !SW && (CF::BN == 96 || CF::BN == 192)) {      // the DAC's conv tiles (fp32 split-3 and bf16): branch-free conv tails (gemm_epilogue, NTAIL >= 2)
     static const bool conv = getenv("ECHO_NT_CONV_TAILS") ? atoi(getenv("ECHO_NT_CONV_TAILS")) != 0 : true;
     if (split && conv && g.ksplit <= 1 && !g.qkv_mode && g.sink && g.bias && g.snake_alpha && g.C2 && !g.colscale && g.act == 0 && g.div == 0.0f &&
         g.acc_scale == 1.0f && g.N >= 4) {

@@ -400,9 +400,13 @@ def load_model_from_path(path: str, device: str = "cuda", dtype: torch.dtype | N
 
 
 def load_fish_ae_from_path(path: str, device: str = "cuda", dtype: torch.dtype | None = torch.float32, config=None) -> DAC:
+    """Local-file counterpart of load_fish_ae_from_hf (reference inference.py:56-76).  `dtype`: None / torch.float32 -> the fp32 autoencoder,
+    torch.bfloat16 -> the bf16 decoder (DAC docstring; the encode path stays fp32); anything else raises ValueError before a file, a device or the
+    library is touched."""
+    from .autoencoder import DACConfig, check_ae_dtype
+    dtype = check_ae_dtype(dtype)
     import safetensors.torch as st
-    from .autoencoder import DACConfig
-    return DAC(config or DACConfig(), st.load_file(path, device="cpu"), device="cuda:0" if device == "cuda" else device)
+    return DAC(config or DACConfig(), st.load_file(path, device="cpu"), device="cuda:0" if device == "cuda" else device, dtype=dtype)
 
 
 def load_pca_state_from_path(path: str, device: str = "cuda") -> PCAState:

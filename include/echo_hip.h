@@ -25,7 +25,7 @@ extern "C" {
 
 #define ECHO_F32 0
 #define ECHO_BF16 1
-#define ECHO_ABI_VERSION 7
+#define ECHO_ABI_VERSION 8
 
 typedef struct echo_ctx echo_ctx;
 
@@ -39,7 +39,9 @@ typedef struct {
   int speaker_patch_size, speaker_model_size, speaker_num_layers, speaker_num_heads, speaker_intermediate_size;
   int timestep_embed_size, adaln_rank;
   int has_latent_encoder;        /* 0 when the checkpoint was loaded with delete_blockwise_modules (inference.py:28-34) */
-  /* DAC decode path (fp32) */
+  /* DAC decode path.  ABI 8: it runs in the context's `precision` - ECHO_F32: fp32 weights and activations (the path of ABI <= 7, bit for bit);
+   * ECHO_BF16: bf16 weights and channels-last bf16 activations on the bf16 MFMA with fp32 accumulation, the reference's own AE dtype
+   * (handler.py:345, inference.py:62-66).  The entry points keep their signatures: fp32 latents in, fp32 waveform out. */
   int dac_latent_dim, dac_decoder_dim, dac_n_rates, dac_rates[8];
   int dac_post_layers, dac_post_heads, dac_post_head_dim, dac_post_ffn, dac_post_window;
   int dac_n_up, dac_up_factors[4];
@@ -69,9 +71,13 @@ void echo_ctx_destroy(echo_ctx* ctx);
 int echo_load_tensor(echo_ctx* ctx, const char* name, const void* data, int dtype, int ndim, const int64_t* shape,
                      int data_on_device);
 int echo_finalize_dit(echo_ctx* ctx, void* stream);    /* pack EchoDiT weights for the kernels, drop the raw copies */
+/* ABI 8, ECHO_BF16 context: the decode-path tensors are expected as the loader of a bf16 DAC prepares them: every checkpoint tensor
+ * rounded to bf16 first, weight-norm folded from the rounded parameters in bf16, conv kernels then reshaped to GEMM form with every decoder channel
+ * count zero-padded to a multiple of 64 (the bf16 K step: 96 -> 128), biases and Snake alphas padded with zeros alike.  They are stored as bf16. */
 int echo_finalize_dac(echo_ctx* ctx, void* stream);
 /* encode-path tensors ("enc.*", prepared by the Python loader: weight-norm folded, conv kernels in GEMM form, codebooks
- * normalised, from_codes operands concatenated; INTEGRATION.md lists them).  Needs echo_finalize_dac first. */
+ * normalised, from_codes operands concatenated; INTEGRATION.md lists them).  Needs echo_finalize_dac first.
+ * ABI 8: the encode path keeps fp32 weights and fp32 kernels in an ECHO_BF16 context too (a bf16 VQ argmax flips codes); pass fp32 tensors. */
 int echo_finalize_dac_encoder(echo_ctx* ctx, void* stream);
 
 /* Position tables computed by the host with the reference's own expressions (exactness for free):
@@ -159,21 +165,26 @@ typedef struct {
 int echo_sample_euler(echo_ctx* ctx, const echo_sampler_params* p, const float* x_init, float* latent_out, void* stream);
 
 /* inference.py:226-229 ae_decode -> autoencoder.py:1128-1132 DAC.decode_zq, one batch item:
- * latent (T, latent_size) fp32 -> wav (T * hop) fp32. */
+ * latent (T, latent_size) fp32 -> wav (T * hop) fp32.
+ * ECHO_BF16 context (ABI 8): the PCA inverse is evaluated in fp32 and rounded to bf16 once (inference.py:227-229), the decoder runs in bf16 and the
+ * waveform comes back as fp32 numbers that are bf16-representable (`.float()` of a bf16 result). */
 int echo_dac_decode(echo_ctx* ctx, const float* latent, int T, float latent_scale, float* wav_out, void* stream);
-/* autoencoder.py:1128-1132 DAC.decode_zq alone: z (T, dac_latent_dim) fp32 CHANNELS-LAST (= z_q[b].T) -> wav (T * hop). */
+/* autoencoder.py:1128-1132 DAC.decode_zq alone: z (T, dac_latent_dim) fp32 CHANNELS-LAST (= z_q[b].T) -> wav (T * hop).
+ * ECHO_BF16 context: z is rounded to bf16 first (`z_q.to(fish_ae.dtype)`); output as for echo_dac_decode. */
 int echo_dac_decode_zq(echo_ctx* ctx, const float* z, int T, float* wav_out, void* stream);
 /* ABI 6: B utterances of T frames each (latent: B x T x latent_size, contiguous) -> wav_out + b * wav_stride (floats).  Same result as B
  * echo_dac_decode calls up to the fp32 summation order of the row-wise GEMMs: the PCA inverse, the post_module transformer and its norm
- * run once on the B * T stacked rows (attention per item and head), the convolution stack per item.  inference.py:226-229 on a batch. */
+ * run once on the B * T stacked rows (attention per item and head), the convolution stack per item.  inference.py:226-229 on a batch.
+ * ECHO_BF16 context: the same schedule on bf16 rows; items agree with single decodes up to the summation order of the row-wise GEMMs. */
 int echo_dac_decode_batch(echo_ctx* ctx, const float* latent, int B, int T, float latent_scale, float* wav_out, int64_t wav_stride, void* stream);
 /* Streaming decode (reference: every conv of autoencoder.py:264-331 is causal, gradio_app.py:43 decodes whole
  * utterances): latent (T, latent_size) fp32 are ALL frames generated so far; the window-limited post_module transformer
  * runs over all of them, the convolutional stack only over frames first_frame.. ; wav_out receives (T - first_frame) * 2048
  * samples.  Samples further than the stack's receptive field (< 10 frames) behind first_frame equal the
- * whole-utterance decode; the caller (DACStream in autoencoder.py) discards that context. */
+ * whole-utterance decode; the caller (DACStream in autoencoder.py) discards that context.  ECHO_BF16 context: as echo_dac_decode. */
 int echo_dac_decode_tail(echo_ctx* ctx, const float* latent, int T, int first_frame, float latent_scale, float* wav_out, void* stream);
-/* inference.py:86-99 PCAState: w = pca_components transposed, (dac_latent_dim, latent_size) row-major fp32; mean (dac_latent_dim). */
+/* inference.py:86-99 PCAState: w = pca_components transposed, (dac_latent_dim, latent_size) row-major fp32; mean (dac_latent_dim).
+ * The operands stay fp32 in an ECHO_BF16 context as well: the reference computes the PCA inverse in fp32 whatever the AE dtype. */
 int echo_set_pca(echo_ctx* ctx, const float* w, const float* mean, int on_device, void* stream);
 int echo_dac_hop(echo_ctx* ctx);
 /* inference.py:218-224 ae_encode = DAC.encode_zq (autoencoder.py:1080-1126) + PCA projection, one item:
@@ -201,6 +212,8 @@ typedef struct {
   int cfg;                       /* plan: 0..4, 6..9 tile configurations (csrc/gemm.hip TileCfg table), 5 = bf16 ping-pong kernel */
   int ksplit; void* ws; int64_t ws_bytes;   /* split-K: fp32 workspace of ksplit * roundup(M,768) * Npad * 4 bytes */
   int split3;                    /* fp32 only: 3 x bf16 MFMA per product (hi/lo operand splitting), ~1e-5 relative error */
+  /* ABI 8, dtype ECHO_BF16 with snake_alpha != NULL (the conv forms of the bf16 DAC decoder): acc * acc_scale + bias [+ residual] and the Snake are
+   * evaluated in fp32 and each output (C, C2) is rounded to bf16 once, at its store; every other bf16 launch rounds after each step as before */
   int fp8;                       /* dtype ECHO_BF16, cfg 5 only: A and W are e4m3 bytes, y = acc * a_scale[m] * w_scale[n]; K % 128 == 0 */
   const float* a_scale; const float* w_scale;
   /* fused QKV(G) tail (model.py:217-232): the N axis is [q | k | v | gate] x qkv_D; q and k get the per-head RMSNorm (qk_w =
