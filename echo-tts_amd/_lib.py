@@ -54,6 +54,12 @@ class EchoSamplerParams(C.Structure):
                 ("steps", C.POINTER(EchoStep)), ("temb", vp)]
 
 
+class EchoSamplerItem(C.Structure):
+    """One utterance of a mixed sampler call (echo_sampler_item, added under ABI 8)."""
+    _fields_ = [("cfg_scale_text", C.c_float), ("cfg_scale_speaker", C.c_float), ("has_truncation", C.c_int), ("init_scale", C.c_float),
+                ("kv_scale", C.c_float), ("kv_max_layers", C.c_int), ("steps", C.POINTER(EchoStep))]
+
+
 class EchoGemmDesc(C.Structure):
     _fields_ = [("A", vp), ("W", vp), ("C", vp), ("C2", vp),
                 ("M", C.c_int), ("N", C.c_int), ("K", C.c_int), ("Npad", C.c_int),
@@ -139,6 +145,9 @@ SIGNATURES = {
     "echo_op_resample": (C.c_int, [vp, c_i64, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, c_i64, vp]),
     "echo_voice_capture": (C.c_int, [vp, C.POINTER(vp), vp]),
     "echo_voice_bind": (C.c_int, [vp, vp, vp]),
+    "echo_sample_euler_items": (C.c_int, [vp, C.POINTER(EchoSamplerParams), C.POINTER(EchoSamplerItem), vp, vp, vp]),
+    "echo_scale_speaker_kv_items": (C.c_int, [vp, C.POINTER(C.c_float), C.POINTER(C.c_int32), C.c_int, vp]),
+    "echo_voice_bind_items": (C.c_int, [vp, C.POINTER(vp), C.c_int, vp]),
     "echo_voice_bytes": (c_i64, [vp]),
     "echo_voice_destroy": (None, [vp]),
     "echo_dac_decode_tail": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_float, vp, vp]),

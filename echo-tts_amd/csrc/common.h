@@ -236,6 +236,36 @@ struct EulerArgs {
 };
 template <typename T> hipError_t launch_euler(const EulerArgs& e, hipStream_t st);
 
+// Mixed sampler call (echo_sample_euler_items): what euler_kernel takes as launch scalars comes from a device table with one entry
+// per (step, utterance); the row layout (R, R_next) stays a property of the launch.
+struct EulerItem {
+  int has_cfg; float s_text, s_spk;
+  int rescale; float r_inv1mt, r_ratio, r_1mt;
+  float dt;
+};
+struct EulerItemsArgs {
+  float* x; const void* v; long ldv; void* xin; long ld_xin;      // as EulerArgs
+  int B, S, L, R, R_next;
+  const EulerItem* items;   // device, B entries: this step's (unused by the init launch)
+  const float* init_scale;  // device, B floats (1.0f = no truncation); read by the init launch only
+  int init;
+};
+template <typename T> hipError_t launch_euler_items(const EulerItemsArgs& e, hipStream_t st);
+
+// Per-item speaker-KV scaling: item b's K | V rows and its V^T rows of layers < nl[b] are multiplied by s[b] (rounding of
+// launch_scale_2d); an item with s == 1 or nl == 0 is not touched.  kv: (nB * Tn, ld) with layer l at columns [l * 2D, (l + 1) * 2D);
+// vt: [layer][nB][D][vld].  16-byte accesses: ld, vld and D are multiples of 16 bytes / sizeof(T).
+#define ECHO_MAX_ITEMS 32
+struct KvItemScales { float s[ECHO_MAX_ITEMS]; int nl[ECHO_MAX_ITEMS]; };
+template <typename T>
+hipError_t launch_scale_kv_items(T* kv, long ld, T* vt, long vld, int nB, int Tn, int D, const KvItemScales& a, hipStream_t st);
+
+// Gather of n batch-1 voices into one speaker cache of batch n and Tn = max T keys: item i's K | V rows < T and V^T columns < T are
+// copied, everything else up to Tn rows / vld columns is written as zero.  tab: device, n entries.
+struct VoiceSrc { const void* kv; const void* vt; int T; int vld; };     // source pitches: kv = ld (the same model), vt = vld
+template <typename T>
+hipError_t launch_voice_gather(const VoiceSrc* tab, int n, T* kv, long ld, T* vt, long vld, int Tn, int D, int layers, hipStream_t st);
+
 // fp32 softmax over rows of a score matrix with per-key bias and optional causal window
 hipError_t launch_softmax_f32(float* s, long ld, int rows_per_batch, int nbatch, int ncols, int ncols_pad,
                               const float* bias, long bias_batch_stride, int heads_per_bias_row,

@@ -313,6 +313,124 @@ __global__ void euler_kernel(const EulerArgs e) {
   for (int r = 0; r < e.R_next; ++r) xin[(r * bs + tok) * e.ld_xin + l] = Num<T>::st(x);
 }
 
+// The same update with per-utterance parameters (echo_sample_euler_items): item = tok / S reads its own table entry.  The arithmetic is
+// euler_kernel's, operation for operation, so an item whose entry equals a uniform call's launch scalars gets the same bits.  R == 3
+// means "some item has CFG at this step"; an item without it takes v_cond as it is (its two un-conditional rows ride along unused).
+template <typename T>
+__global__ void euler_items_kernel(const EulerItemsArgs e) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long n = (long)e.B * e.S * e.L;
+  if (i >= n) return;
+  const long tok = i / e.L;
+  const int l = (int)(i - tok * e.L);
+  const int item = (int)(tok / e.S);
+  const long bs = (long)e.B * e.S;
+  float x = e.x[i];
+  if (e.init) {
+    const float s = e.init_scale[item];
+    if (s != 1.0f) x = __fmul_rn(x, s);
+  } else {
+    const EulerItem it = e.items[item];
+    const T* v = (const T*)e.v;
+    float vp = Num<T>::ld(v[tok * e.ldv + l]);
+    if (e.R == 3 && it.has_cfg) {
+      const float vut = Num<T>::ld(v[(bs + tok) * e.ldv + l]);
+      const float vus = Num<T>::ld(v[(2 * bs + tok) * e.ldv + l]);
+      const float a = __fmul_rn(it.s_text, __fsub_rn(vp, vut));
+      const float b = __fmul_rn(it.s_spk, __fsub_rn(vp, vus));
+      vp = __fadd_rn(__fadd_rn(vp, a), b);
+    }
+    if (it.rescale) {
+      float t = __fadd_rn(__fmul_rn(it.r_1mt, vp), x);
+      t = __fsub_rn(__fmul_rn(it.r_ratio, t), x);
+      vp = __fmul_rn(it.r_inv1mt, t);
+    }
+    x = __fadd_rn(x, __fmul_rn(vp, it.dt));
+  }
+  e.x[i] = x;
+  T* xin = (T*)e.xin;
+  for (int r = 0; r < e.R_next; ++r) xin[(r * bs + tok) * e.ld_xin + l] = Num<T>::st(x);
+}
+
+// 16 bytes of T
+template <typename T> union Pack16 { uint4 u; T e[16 / sizeof(T)]; };
+
+// blockIdx.y = item; the x dimension strides over the item's 16-byte vectors: first its K | V rows (Tn rows of nl * 2D contiguous
+// columns), then its V^T rows of the nl layers (D rows of Tn columns each; the last vector of a row is scaled up to column Tn only).
+template <typename T>
+__global__ void __launch_bounds__(256) scale_kv_items_kernel(T* __restrict__ kv, long ld, T* __restrict__ vt, long vld, int nB, int Tn, int D,
+                                                             const KvItemScales a) {
+  constexpr int V = 16 / (int)sizeof(T);
+  const int b = blockIdx.y;
+  const float s = a.s[b];
+  const int nl = a.nl[b];
+  if (s == 1.0f || nl <= 0) return;
+  const long kvv = (long)nl * 2 * D / V;
+  const long n_kv = (long)Tn * kvv;
+  const int tv = (Tn + V - 1) / V;
+  const long total = n_kv + (long)nl * D * tv;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+    T* p;
+    int valid = V;
+    if (i < n_kv) {
+      const long r = i / kvv, c = i - r * kvv;
+      p = kv + ((long)b * Tn + r) * ld + c * V;
+    } else {
+      const long j = i - n_kv;
+      const long row = j / tv;                 // l * D + d
+      const int c = (int)(j - row * tv);
+      const long l = row / D, d = row - l * D;
+      p = vt + ((l * nB + b) * D + d) * vld + (long)c * V;
+      valid = min(V, Tn - c * V);
+    }
+    Pack16<T> w;
+    w.u = *(const uint4*)p;
+#pragma unroll
+    for (int k = 0; k < V; ++k)
+      if (k < valid) w.e[k] = Num<T>::st(__fmul_rn(Num<T>::ld(w.e[k]), s));
+    *(uint4*)p = w.u;
+  }
+}
+
+// blockIdx.y = item; x strides over the item's destination vectors: Tn rows of ld columns of K | V, then layers * D rows of vld
+// columns of V^T.  Elements past the item's own key count are zeros: a masked key is multiplied by a zero probability, and
+// 0 x (whatever the buffer held before) must be 0.
+template <typename T>
+__global__ void __launch_bounds__(256) voice_gather_kernel(const VoiceSrc* __restrict__ tab, T* __restrict__ kv, long ld, T* __restrict__ vt, long vld,
+                                                           int nB, int Tn, int D, int layers) {
+  constexpr int V = 16 / (int)sizeof(T);
+  const int b = blockIdx.y;
+  const VoiceSrc src = tab[b];
+  const long kvv = ld / V;
+  const long n_kv = (long)Tn * kvv;
+  const int tv = (int)(vld / V);
+  const long total = n_kv + (long)layers * D * tv;
+  const uint4 zero = {0u, 0u, 0u, 0u};
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+    if (i < n_kv) {
+      const long r = i / kvv, c = i - r * kvv;
+      uint4 w = zero;
+      if (r < src.T) w = *(const uint4*)((const T*)src.kv + r * ld + c * V);
+      *(uint4*)(kv + ((long)b * Tn + r) * ld + c * V) = w;
+    } else {
+      const long j = i - n_kv;
+      const long row = j / tv;                 // l * D + d: the source has batch 1, so its row index is the same
+      const int c = (int)(j - row * tv);
+      const long l = row / D, d = row - l * D;
+      Pack16<T> w;
+      w.u = zero;
+      const int valid = src.T - c * V;         // columns of this vector the voice owns (<= 0: none)
+      if (valid > 0) {
+        w.u = *(const uint4*)((const T*)src.vt + row * src.vld + (long)c * V);      // c * V < T <= src.vld, a multiple of 64: in bounds
+#pragma unroll
+        for (int k = 0; k < V; ++k)
+          if (k >= valid) w.e[k] = (T)0;
+      }
+      *(uint4*)(vt + ((l * nB + b) * D + d) * vld + (long)c * V) = w.u;
+    }
+  }
+}
+
 // ------------------------------------------------------------------ fp32 softmax with key bias / causal window
 __global__ void __launch_bounds__(256) softmax_f32_kernel(float* __restrict__ s, long ld, int rows_per_batch, long total_rows, int ncols,
                                                           int ncols_pad, const float* __restrict__ bias, long bias_batch_stride,
@@ -633,6 +751,36 @@ template <typename T> hipError_t launch_euler(const EulerArgs& e, hipStream_t st
   hipLaunchKernelGGL(euler_kernel<T>, grid1d((long)e.B * e.S * e.L), dim3(256), 0, st, e);
   return hipGetLastError();
 }
+template <typename T> hipError_t launch_euler_items(const EulerItemsArgs& e, hipStream_t st) {
+  if (!e.x || !e.xin || (e.init ? !e.init_scale : (!e.items || !e.v)) || e.B < 1 || e.S < 1 || e.L < 1) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(euler_items_kernel<T>, grid1d((long)e.B * e.S * e.L), dim3(256), 0, st, e);
+  return hipGetLastError();
+}
+// bandwidth kernels: enough workgroups for a few rounds of the 256 CUs, the rest of an item's vectors in the grid-stride loop
+static inline unsigned items_grid_x(long vectors) { return (unsigned)std::max(1L, std::min((vectors + 255) / 256, 2048L)); }
+template <typename T>
+hipError_t launch_scale_kv_items(T* kv, long ld, T* vt, long vld, int nB, int Tn, int D, const KvItemScales& a, hipStream_t st) {
+  constexpr int V = 16 / (int)sizeof(T);
+  if (nB < 1 || nB > ECHO_MAX_ITEMS || Tn < 1 || D < 1 || (2 * D) % V || ld % V || vld % V || vld < (long)(Tn + V - 1) / V * V ||
+      ((uintptr_t)kv & 15) || ((uintptr_t)vt & 15)) return hipErrorInvalidValue;
+  long most = 0;
+  for (int b = 0; b < nB; ++b) {
+    if (a.nl[b] < 0 || (long)a.nl[b] * 2 * D > ld) return hipErrorInvalidValue;
+    if (a.s[b] != 1.0f) most = std::max(most, (long)a.nl[b] * (2L * D / V * Tn + (long)D * ((Tn + V - 1) / V)));
+  }
+  if (most == 0) return hipSuccess;
+  hipLaunchKernelGGL(scale_kv_items_kernel<T>, dim3(items_grid_x(most), nB), dim3(256), 0, st, kv, ld, vt, vld, nB, Tn, D, a);
+  return hipGetLastError();
+}
+template <typename T>
+hipError_t launch_voice_gather(const VoiceSrc* tab, int n, T* kv, long ld, T* vt, long vld, int Tn, int D, int layers, hipStream_t st) {
+  constexpr int V = 16 / (int)sizeof(T);
+  if (!tab || n < 1 || n > ECHO_MAX_ITEMS || Tn < 1 || D < 1 || layers < 1 || ld % V || vld % V || vld < Tn ||
+      ((uintptr_t)kv & 15) || ((uintptr_t)vt & 15)) return hipErrorInvalidValue;
+  const long vectors = (long)Tn * (ld / V) + (long)layers * D * (vld / V);
+  hipLaunchKernelGGL(voice_gather_kernel<T>, dim3(items_grid_x(vectors), n), dim3(256), 0, st, tab, kv, ld, vt, vld, n, Tn, D, layers);
+  return hipGetLastError();
+}
 hipError_t launch_softmax_f32(float* s, long ld, int rows_per_batch, int nbatch, int ncols, int ncols_pad, const float* bias,
                               long bias_batch_stride, int heads_per_bias_row, int causal, int window, hipStream_t st) {
   const long total = (long)rows_per_batch * nbatch;
@@ -699,6 +847,9 @@ hipError_t launch_mask_to_bias(const uint8_t* mask, float* bias, long n, hipStre
   template hipError_t launch_mod_finalize<T>(T*, long, int, hipStream_t);                                                    \
   template hipError_t launch_convert_from_f32<T>(const float*, long, T*, long, int, int, int, hipStream_t);                  \
   template hipError_t launch_convert_to_f32<T>(const T*, long, float*, long, int, int, hipStream_t);                         \
-  template hipError_t launch_euler<T>(const EulerArgs&, hipStream_t);
+  template hipError_t launch_euler<T>(const EulerArgs&, hipStream_t);                                                        \
+  template hipError_t launch_euler_items<T>(const EulerItemsArgs&, hipStream_t);                                             \
+  template hipError_t launch_scale_kv_items<T>(T*, long, T*, long, int, int, int, const KvItemScales&, hipStream_t);         \
+  template hipError_t launch_voice_gather<T>(const VoiceSrc*, int, T*, long, T*, long, int, int, int, hipStream_t);
 INST(bf16_t)
 INST(float)

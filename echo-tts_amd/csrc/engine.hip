@@ -202,6 +202,42 @@ struct EngineBase {
   virtual int fp8_calibrate(int on) = 0;
   virtual int fp8_calibration(float* out, int n) = 0;
   virtual int fp8_set_static(const float* s, int n) = 0;
+  // mixed batches (added under ABI 8): per-utterance sampler parameters, speaker-KV scaling and cached voices in one call
+  virtual int sample_euler_items(const echo_sampler_params* p, const echo_sampler_item* items, const float* x0, float* out, hipStream_t st) = 0;
+  virtual int scale_speaker_kv_items(const float* scales, const int32_t* max_layers, int n, hipStream_t st) = 0;
+  virtual int voice_bind_items(const struct VoiceSnap* const* v, int n, hipStream_t st) = 0;
+};
+
+// Small host tables go to the device through a ring of pinned staging slots, without a host sync (the pattern of push_nkeys): a
+// slot is reused only after the copy that read it has executed.
+struct HostStage {
+  static constexpr int SLOTS = 8;
+  char* base = nullptr; size_t slot_bytes = 0;
+  hipEvent_t ev[SLOTS] = {}; bool used[SLOTS] = {}; int next = 0;
+  hipError_t push(const void* src, size_t bytes, void* dst_dev, hipStream_t st) {
+    hipError_t e;
+    if (bytes > slot_bytes) {                  // grows while the geometry is new; never once warm
+      for (int i = 0; i < SLOTS; ++i) if (used[i]) { if ((e = hipEventSynchronize(ev[i])) != hipSuccess) return e; used[i] = false; }
+      if (base) { if ((e = hipHostFree(base)) != hipSuccess) return e; base = nullptr; slot_bytes = 0; }
+      const size_t sb = (size_t)rup((long)bytes, 4096);
+      if ((e = hipHostMalloc((void**)&base, sb * SLOTS, hipHostMallocDefault)) != hipSuccess) return e;
+      slot_bytes = sb;
+    }
+    const int s = next;
+    next = (next + 1) % SLOTS;
+    if (!ev[s] && (e = hipEventCreateWithFlags(&ev[s], hipEventDisableTiming)) != hipSuccess) return e;
+    if (used[s] && (e = hipEventSynchronize(ev[s])) != hipSuccess) return e;
+    memcpy(base + (size_t)s * slot_bytes, src, bytes);
+    if ((e = hipMemcpyAsync(dst_dev, base + (size_t)s * slot_bytes, bytes, hipMemcpyHostToDevice, st)) != hipSuccess) return e;
+    if ((e = hipEventRecord(ev[s], st)) != hipSuccess) return e;
+    used[s] = true;
+    return hipSuccess;
+  }
+  void release() {
+    if (base) (void)hipHostFree(base);
+    for (auto& e : ev) if (e) (void)hipEventDestroy(e);
+    base = nullptr; slot_bytes = 0;
+  }
 };
 
 #define CK(x)                                            \
@@ -222,6 +258,7 @@ struct Engine : EngineBase {
 
   ~Engine() override {
     if (nk_pinned) (void)hipHostFree(nk_pinned);
+    stage_items.release();
     for (auto& e : nk_ev) if (e) (void)hipEventDestroy(e);
     for (void* p : owned) (void)hipFree(p);
     for (DevBuf* b : all_bufs()) b->release();
@@ -253,12 +290,14 @@ struct Engine : EngineBase {
   DevBuf b_mod, b_c1, b_c2, b_cond, b_sc, b_dn, b_xstate, b_vf32;
   DevBuf b_ex, b_exn, b_eqkvg, b_evt, b_eattn, b_eh, b_ein, b_enk;
   DevBuf b_dacA, b_dacB, b_dacC, b_dq, b_dscore, b_dvt, b_dmisc;
+  DevBuf b_items, b_voice_tab;      // mixed batches: the sampler's (step, item) table | the voice gather's source table
+  HostStage stage_items;
   std::vector<DevBuf*> all_bufs() {
     return {&b_kv_text, &b_vt_text, &b_kv_spk, &b_vt_spk, &b_kv_lat, &b_vt_lat, &b_nkeys, &b_bias_text, &b_bias_spk,
             &b_xin, &b_x, &b_xn, &b_qkvg, &b_vt_self, &b_attn, &b_h, &b_vout, &b_scores, &b_biasrows, &b_segmeta, &b_attn_redo,
             &b_mod, &b_c1, &b_c2, &b_cond, &b_sc, &b_dn, &b_xstate, &b_vf32,
             &b_ex, &b_exn, &b_eqkvg, &b_evt, &b_eattn, &b_eh, &b_ein, &b_enk,
-            &b_dacA, &b_dacB, &b_dacC, &b_dq, &b_dscore, &b_dvt, &b_dmisc};
+            &b_dacA, &b_dacB, &b_dacC, &b_dq, &b_dscore, &b_dvt, &b_dmisc, &b_items, &b_voice_tab};
   }
   // text / speaker / latent cache geometry
   int kvB = 0;          // batch size of the text cache (= utterances per sampler call)
@@ -977,6 +1016,36 @@ struct Engine : EngineBase {
     return ECHO_OK;
   }
 
+  // Per-item form (mixed batches): n entries, one per utterance; n is the speaker cache's batch or a multiple of it, and utterances
+  // that share a voice slot (b % spkB) must ask for the same scaling - the slot exists once.
+  int kv_slot_scales(const float* scales, const int32_t* max_layers, int n, KvItemScales& out) {
+    const int L = cfg.num_layers;
+    if (!scales || !max_layers) return fail("speaker-KV scaling per item: null scales / max_layers");
+    if (spkB < 1 || n < 1 || n > ECHO_MAX_ITEMS || n % spkB) return fail("speaker-KV scaling per item: the number of items must be a multiple of the speaker cache's batch size");
+    for (int b = 0; b < n; ++b) {
+      if (!std::isfinite(scales[b])) return fail("speaker-KV scaling per item: a scale is not finite");
+      const int nl = max_layers[b] < 0 ? L : std::min((int)max_layers[b], L);
+      const int slot = b % spkB;
+      if (b < spkB) { out.s[slot] = scales[b]; out.nl[slot] = nl; }
+      else if (out.s[slot] != scales[b] || (scales[b] != 1.0f && out.nl[slot] != nl))
+        return fail("speaker-KV scaling per item: utterances that share a voice slot carry different scaling parameters");
+    }
+    return ECHO_OK;
+  }
+  int launch_kv_slot_scales(const KvItemScales& a, hipStream_t st) {
+    const int D = cfg.model_size, L = cfg.num_layers;
+    CK(launch_scale_kv_items<T>(b_kv_spk.as<T>(), (long)L * 2 * D, b_vt_spk.as<T>(), spk_vld, spkB, spk_T, D, a, st));
+    return ECHO_OK;
+  }
+  int scale_speaker_kv_items(const float* scales, const int32_t* max_layers, int n, hipStream_t st) override {
+    if (!dit_ready) return fail("echo_finalize_dit was not called");
+    KvItemScales a;
+    memset(&a, 0, sizeof(a));
+    CKI(kv_slot_scales(scales, max_layers, n, a));
+    if (spk_T == 0) return ECHO_OK;
+    return launch_kv_slot_scales(a, st);
+  }
+
   // Per-voice cache (the reference re-runs get_kv_cache_speaker for every chunk: handler.py:750-758,
   // inference.py:333-340, model.py:615-621).  capture: device copy of the speaker K/V + Vᵀ of all layers as they stand
   // (call it right after echo_encode_speaker, before any speaker-KV scaling); bind: copy it back as this context's speaker
@@ -1018,6 +1087,50 @@ struct Engine : EngineBase {
       if (spk_has_bias) {
         CK(b_bias_spk.reserve(v->bias_bytes));
         CK(hipMemcpyAsync(b_bias_spk.p, v->bias.p, v->bias_bytes, hipMemcpyDeviceToDevice, st));
+      }
+    }
+    return ECHO_OK;
+  }
+
+  // n batch-1 voices become this context's speaker cache of batch n (one voice per utterance of a mixed call).  The cache takes the
+  // largest key count; voice_gather_kernel writes every item's rows and Vᵀ columns beyond its own count as zeros.
+  int voice_bind_items(const VoiceSnap* const* vs, int n, hipStream_t st) override {
+    if (!dit_ready) return fail("echo_finalize_dit was not called");
+    if (!vs || n < 1 || n > ECHO_MAX_ITEMS || 3 * n > MAXROWS) return fail("voice bind per item: 1..32 voices expected");
+    int Tn = 0; bool any_bias = false;
+    for (int i = 0; i < n; ++i) {
+      const VoiceSnap* v = vs[i];
+      if (!v) return fail("null voice");
+      if (v->device != device || v->precision != cfg.precision || v->model_size != cfg.model_size || v->num_layers != cfg.num_layers)
+        return fail("voice was captured from a different model / device / precision");
+      if (v->B != 1 || (int)v->nk.size() != 1) return fail("voice bind per item: every voice must have been captured with batch size 1");
+      if (v->T > 0 && (v->vld < v->T || v->vld % 64 || !v->kv.p || !v->vt.p)) return fail("voice bind per item: malformed voice");
+      Tn = std::max(Tn, v->T);
+      any_bias = any_bias || (v->has_bias && v->T > 0);
+    }
+    const int D = cfg.model_size, L = cfg.num_layers;
+    const long ld = (long)L * 2 * D;
+    spkB = n; spk_T = Tn; spk_pad = (int)rup(Tn, 128); spk_vld = (int)rup(Tn, 64);
+    spk_nk.resize(n);
+    for (int i = 0; i < n; ++i) spk_nk[i] = vs[i]->T > 0 ? vs[i]->nk[0] : 0;
+    spk_has_bias = any_bias; spk_bias_ld = spk_vld;
+    if (Tn == 0) return ECHO_OK;
+    CK(b_kv_spk.reserve((size_t)((long)n * Tn + 256) * ld * sizeof(T)));
+    CK(b_vt_spk.reserve((size_t)L * n * D * spk_vld * sizeof(T) + 4096));
+    CK(b_voice_tab.reserve(sizeof(VoiceSrc) * ECHO_MAX_ITEMS));
+    VoiceSrc tab[ECHO_MAX_ITEMS];
+    memset(tab, 0, sizeof(tab));
+    for (int i = 0; i < n; ++i) { tab[i].kv = vs[i]->kv.p; tab[i].vt = vs[i]->vt.p; tab[i].T = vs[i]->T; tab[i].vld = vs[i]->vld; }
+    CK(stage_items.push(tab, sizeof(VoiceSrc) * n, b_voice_tab.p, st));
+    CK(launch_voice_gather<T>(b_voice_tab.as<VoiceSrc>(), n, b_kv_spk.as<T>(), ld, b_vt_spk.as<T>(), spk_vld, Tn, D, L, st));
+    if (any_bias) {     // a key bias is carried only if some voice has one; the others get 0 on their keys
+      CK(b_bias_spk.reserve((size_t)n * spk_bias_ld * sizeof(float)));
+      CK(hipMemsetAsync(b_bias_spk.p, 0, (size_t)n * spk_bias_ld * sizeof(float), st));
+      for (int i = 0; i < n; ++i) {
+        const VoiceSnap* v = vs[i];
+        if (!v->has_bias || v->T == 0 || !v->bias.p) continue;
+        const size_t cnt = (size_t)std::min((long)v->T, v->bias_ld);
+        CK(hipMemcpyAsync(b_bias_spk.as<float>() + (long)i * spk_bias_ld, v->bias.p, cnt * sizeof(float), hipMemcpyDeviceToDevice, st));
       }
     }
     return ECHO_OK;
@@ -1366,6 +1479,103 @@ struct Engine : EngineBase {
       e.rescale = sp.rescale; e.r_inv1mt = sp.r_inv1mt; e.r_ratio = sp.r_ratio; e.r_1mt = sp.r_1mt;
       e.dt = sp.dt;
       CK(launch_euler<T>(e, st));
+    }
+    CK(hipMemcpyAsync(out, xs, (size_t)B * S * Lz * sizeof(float), hipMemcpyDeviceToDevice, st));
+    if (profiling) {
+      CK(hipEventRecord(ev[2], st));
+      CK(hipEventSynchronize(ev[2]));
+      CK(hipEventElapsedTime(&prof.ms_mod, ev[0], ev[1]));
+      CK(hipEventElapsedTime(&prof.ms_steps, ev[1], ev[2]));
+      prof.ms_total = prof.ms_mod + prof.ms_steps;
+      collect_gemm_times();
+    }
+    return ECHO_OK;
+  }
+  // The same loop with per-utterance parameters (mixed batches).  `p` supplies B, S, num_steps, start_pos, use_latent and temb; every
+  // item brings its own scales, truncation, KV scale and step table.  A step runs the 3B-row CFG layout when ANY item has CFG at
+  // it (the `row % B` KV addressing stays), so items outside their window ride along in the un-conditional rows.
+  int sample_euler_items(const echo_sampler_params* p, const echo_sampler_item* items, const float* x0, float* out, hipStream_t st) override {
+    if (!dit_ready) return fail("echo_finalize_dit was not called");
+    if (!p || !items) return fail("mixed sampler call: null params / items");
+    const int B = p->B, S = p->S, N = p->num_steps, Lz = cfg.latent_size;
+    if (B != kvB) return fail("mixed sampler call: B differs from the batch size of the text cache");
+    if (B < 1 || 3 * B > MAXROWS) return fail("mixed sampler call: at most 32 items per call");
+    if (S < 1 || N < 1 || !x0 || !out || !p->temb) return fail("bad sampler params");
+    if (spk_T > 0 && (spkB < 1 || kvB % spkB)) return fail("the speaker cache's batch size must divide the text cache's");
+    for (int b = 0; b < B; ++b) {
+      if (!items[b].steps) return fail("mixed sampler call: an item has no step table");
+      for (int i = 0; i < N; ++i)
+        if (items[b].steps[i].dt != items[0].steps[i].dt)
+          return fail("mixed sampler call: the items' schedules differ (dt); all items of a call share num_steps and the t schedule");
+    }
+    // host side of the step loop, prepared up front: row sets, the (step, item) table, the speaker-KV un-scaling per voice slot
+    std::vector<char> any_cfg(N, 0);
+    std::vector<EulerItem> tab((size_t)N * B);
+    std::vector<float> init(B);
+    std::vector<KvItemScales> unscale(N);
+    std::vector<char> has_unscale(N, 0);
+    std::vector<float> us(B);
+    std::vector<int32_t> ul(B);
+    for (int b = 0; b < B; ++b) init[b] = items[b].has_truncation ? items[b].init_scale : 1.0f;
+    for (int i = 0; i < N; ++i) {
+      for (int b = 0; b < B; ++b) {
+        const echo_step& sp = items[b].steps[i];
+        EulerItem& t = tab[(size_t)i * B + b];
+        t.has_cfg = sp.has_cfg ? 1 : 0; t.s_text = items[b].cfg_scale_text; t.s_spk = items[b].cfg_scale_speaker;
+        t.rescale = sp.rescale; t.r_inv1mt = sp.r_inv1mt; t.r_ratio = sp.r_ratio; t.r_1mt = sp.r_1mt; t.dt = sp.dt;
+        if (sp.has_cfg) any_cfg[i] = 1;
+        us[b] = 1.0f; ul[b] = items[b].kv_max_layers;
+        if (sp.kv_unscale_after && spk_T > 0) {
+          if (!(items[b].kv_scale != 0.0f) || !std::isfinite(items[b].kv_scale)) return fail("mixed sampler call: kv_scale must be finite and non-zero");
+          us[b] = 1.0f / items[b].kv_scale;
+          has_unscale[i] = 1;
+        }
+      }
+      memset(&unscale[i], 0, sizeof(KvItemScales));
+      if (has_unscale[i]) CKI(kv_slot_scales(us.data(), ul.data(), B, unscale[i]));
+    }
+    const int rows3 = 3 * B;
+    CKI(reserve_dit_ws(rows3 * S, rows3, S));
+    CK(b_xstate.reserve((size_t)B * S * Lz * sizeof(float)));
+    const size_t tab_bytes = tab.size() * sizeof(EulerItem), init_bytes = (size_t)B * sizeof(float);
+    CK(b_items.reserve(tab_bytes + init_bytes));
+    float* xs = b_xstate.as<float>();
+    if (profiling) {
+      for (auto& e : ev) if (!e) CK(hipEventCreate(&e));
+      gemm_events_used = 0; attn_events_used = 0;
+      CK(hipEventRecord(ev[0], st));
+    }
+    {   // one copy: [N][B] step entries, then the B init scales
+      std::vector<char> blob(tab_bytes + init_bytes);
+      memcpy(blob.data(), tab.data(), tab_bytes);
+      memcpy(blob.data() + tab_bytes, init.data(), init_bytes);
+      CK(stage_items.push(blob.data(), blob.size(), b_items.p, st));
+    }
+    const EulerItem* tab_dev = b_items.as<EulerItem>();
+    CK(hipMemcpyAsync(xs, x0, (size_t)B * S * Lz * sizeof(float), hipMemcpyDeviceToDevice, st));
+    CKI(compute_mod((const T*)p->temb, N, st));
+    if (profiling) CK(hipEventRecord(ev[1], st));
+    std::vector<int32_t> ton(rows3, 1), son(rows3, 1);
+    for (int b = 0; b < B; ++b) { ton[B + b] = 0; son[2 * B + b] = 0; }
+    set_row_keys(rows3, B, S, p->start_pos, p->use_latent != 0, ton.data(), son.data());
+    CKI(push_nkeys(st));
+    const long modstride = (long)2 * cfg.num_layers * 3 * cfg.model_size;
+    EulerItemsArgs e;
+    memset(&e, 0, sizeof(e));
+    e.x = xs; e.v = b_vout.p; e.ldv = 128; e.xin = b_xin.p; e.ld_xin = lat_pad;
+    e.B = B; e.S = S; e.L = Lz; e.R = 1;
+    e.R_next = any_cfg[0] ? 3 : 1;
+    e.init = 1; e.init_scale = (const float*)((const char*)b_items.p + tab_bytes); e.items = tab_dev;
+    CK(launch_euler_items<T>(e, st));
+    for (int i = 0; i < N; ++i) {
+      const int rows = any_cfg[i] ? rows3 : B;
+      CKI(forward_rows(rows, B, S, p->start_pos, p->use_latent != 0, b_mod.as<T>() + (long)i * modstride, st));
+      if (has_unscale[i]) CKI(launch_kv_slot_scales(unscale[i], st));
+      e.init = 0;
+      e.R = any_cfg[i] ? 3 : 1;
+      e.R_next = (i + 1 < N && any_cfg[i + 1]) ? 3 : 1;
+      e.items = tab_dev + (size_t)i * B;
+      CK(launch_euler_items<T>(e, st));
     }
     CK(hipMemcpyAsync(out, xs, (size_t)B * S * Lz * sizeof(float), hipMemcpyDeviceToDevice, st));
     if (profiling) {
@@ -2246,6 +2456,23 @@ int echo_voice_capture(echo_ctx* ctx, echo_voice** out, void* stream) {
 }
 int echo_voice_bind(echo_ctx* ctx, const echo_voice* voice, void* stream) {
   return ctx && voice ? ctx->eng->voice_bind(voice->v, (hipStream_t)stream) : ECHO_ERR;
+}
+int echo_voice_bind_items(echo_ctx* ctx, const echo_voice* const* voices, int n, void* stream) {
+  if (!ctx) return ECHO_ERR;
+  if (!voices || n < 1 || n > ECHO_MAX_ITEMS) return ctx->eng->fail("voice bind per item: 1..32 voices expected");
+  const VoiceSnap* vs[ECHO_MAX_ITEMS];
+  for (int i = 0; i < n; ++i) {
+    if (!voices[i] || !voices[i]->v) return ctx->eng->fail("null voice");
+    vs[i] = voices[i]->v;
+  }
+  return ctx->eng->voice_bind_items(vs, n, (hipStream_t)stream);
+}
+int echo_scale_speaker_kv_items(echo_ctx* ctx, const float* scales_host, const int32_t* max_layers_host, int n, void* stream) {
+  return ctx ? ctx->eng->scale_speaker_kv_items(scales_host, max_layers_host, n, (hipStream_t)stream) : ECHO_ERR;
+}
+int echo_sample_euler_items(echo_ctx* ctx, const echo_sampler_params* p, const echo_sampler_item* items, const float* x_init, float* latent_out,
+                            void* stream) {
+  return ctx ? ctx->eng->sample_euler_items(p, items, x_init, latent_out, (hipStream_t)stream) : ECHO_ERR;
 }
 int64_t echo_voice_bytes(const echo_voice* voice) {
   return voice && voice->v ? (int64_t)(voice->v->kv_bytes + voice->v->vt_bytes + voice->v->bias_bytes) : 0;

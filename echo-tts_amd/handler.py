@@ -343,6 +343,144 @@ def synthesize(job_input: Dict, model, fish_ae, pca_state, speaker_latent: Optio
         return {"error": str(e), "error_type": type(e).__name__, "traceback": traceback.format_exc()}
 
 
+# --------------------------------------------------------------------------- several jobs through shared sampler calls
+ITEM_PARAM_KEYS = tuple(k for k in SAMPLER_DEFAULTS if k != "sequence_length")      # per utterance; sequence_length and num_steps group calls
+
+
+def plan_mixed_batches(job_inputs: List[Dict], max_batch: int = 24) -> Tuple[List[Dict], List[Dict]]:
+    """Pure planning step of `synthesize_many` (no device work).  Every job is validated as `synthesize` validates it and chunked
+    as `_run_job` chunks it; the chunks of all good jobs are grouped by (num_steps, sequence_length) - the two parameters a
+    sampler call cannot mix - and cut into calls of at most `max_batch` rows, in job order, chunk order within a job.
+
+    Returns (jobs, calls):
+    jobs[j]  = {"error": ...} for a bad job (it takes no row anywhere), else {"pieces", "seed", "item", "sequence_length",
+               "normalize_boundaries", "enable_crossfade", "speaker_voice", "text_length"};
+    calls[c] = {"num_steps", "sequence_length", "rows": [{"job", "chunk", "text", "seed"}, ...]}; a row's seed is
+               seed + chunk * 1000 (handler.py:747-759)."""
+    max_batch = max(1, min(int(max_batch), 32))
+    jobs: List[Dict] = []
+    groups: "OrderedDict[Tuple[int, int], List[Dict]]" = OrderedDict()
+    for j, job_input in enumerate(job_inputs):
+        try:
+            if not isinstance(job_input, dict):
+                raise ValueError("job input must be a dict")
+            bad = _validate_text(job_input)
+            if bad:
+                jobs.append(bad)
+                continue
+            text = job_input.get("text")
+            parameters = job_input.get("parameters") or {}
+            seed = int(parameters.get("seed", job_input.get("seed", 0)))
+            try:
+                max_chars = int(parameters.get("max_chars_per_chunk", 300))
+            except Exception:
+                max_chars = 300
+            target_duration = parameters.get("target_duration_seconds", 10.0)
+            pieces = chunk_text_for_audio(text, max_chars=max_chars, target_duration_seconds=target_duration) if max_chars and max_chars > 0 else [text]
+            if not pieces:
+                raise ValueError("Text is empty after normalization")
+            seq = parameters.get("sequence_length", SAMPLER_DEFAULTS["sequence_length"])
+            seq = 640 if seq is None else int(seq)
+            item = {k: parameters.get(k, SAMPLER_DEFAULTS[k]) for k in ITEM_PARAM_KEYS}
+            item["num_steps"] = int(item["num_steps"])
+            if item["num_steps"] < 1 or seq < 1:
+                raise ValueError("num_steps and sequence_length must be positive")
+            voice = job_input.get("speaker_voice")
+            jobs.append({"pieces": pieces, "seed": seed, "item": item, "sequence_length": seq,
+                         "normalize_boundaries": parameters.get("normalize_boundaries", True),
+                         "enable_crossfade": parameters.get("enable_crossfade", True),
+                         "speaker_voice": str(voice) if voice else None, "text_length": len(text)})
+            rows = groups.setdefault((item["num_steps"], seq), [])
+            for c, piece in enumerate(pieces):
+                rows.append({"job": j, "chunk": c, "text": piece, "seed": seed + c * 1000})
+        except Exception as e:
+            jobs.append({"error": str(e), "error_type": type(e).__name__, "traceback": traceback.format_exc()})
+    calls = []
+    for (num_steps, seq), rows in groups.items():
+        for r0 in range(0, len(rows), max_batch):
+            calls.append({"num_steps": num_steps, "sequence_length": seq, "rows": rows[r0:r0 + max_batch]})
+    return jobs, calls
+
+
+_NO_VOICE = "\0no-voice"      # cache key of the one-masked-key voice jobs without a speaker_voice get (inference.py:341-346)
+
+
+@torch.inference_mode()
+def synthesize_many(job_inputs: List[Dict], model, fish_ae, pca_state, voices=None, max_batch: int = 24) -> List[Dict]:
+    """Several jobs at once: the text chunks of ALL jobs share sampler calls of up to `max_batch` rows, each row with its own
+    request parameters, seed and cached voice (`inference.sample_euler_items`, `EchoDiT.bind_voices`).  Only `num_steps` and
+    `sequence_length` cannot be mixed inside a call; jobs are grouped by them (`plan_mixed_batches`).
+
+    `voices`: a `VoiceCache`, or a dict `speaker_voice` name -> (speaker_latent, speaker_mask) or 44.1 kHz audio (1, n); a job
+    names its voice with `speaker_voice`, a job without one gets the one-masked-key voice of `sample_pipeline`.  Returns one dict
+    per job, in job order: what `synthesize` returns for it, or its own error dict - a bad job does not disturb the others.
+    Single-rank: the chunks never enter the data-parallel path of `_run_job`."""
+    from .inference import ae_decode, find_flattening_points, get_speaker_latent_and_mask, get_text_input_ids_and_mask, sample_euler_items
+    jobs, calls = plan_mixed_batches(job_inputs, max_batch)
+    device, dtype, lz = model.device, model.dtype, model.config.latent_size
+    cache = voices if isinstance(voices, VoiceCache) else VoiceCache()
+    registry = {} if isinstance(voices, VoiceCache) or voices is None else dict(voices)
+
+    def voice_of(name: Optional[str]):
+        key = _NO_VOICE if name is None else name
+        if cache.latent(key) is None:
+            if name is None:
+                lat, mask = torch.zeros((1, 4, lz), device=device, dtype=dtype), torch.zeros((1, 4), device=device, dtype=torch.bool)
+            else:
+                src = registry.get(name)
+                if src is None:
+                    return None
+                lat, mask = src if isinstance(src, (tuple, list)) else get_speaker_latent_and_mask(fish_ae, pca_state, src.to(device))
+            cache.put_latent(key, lat.to(device, dtype), mask)
+        return cache.speaker_kv(model, key)
+
+    for j, job in enumerate(jobs):       # an unknown voice fails its own job before any row is spent on it
+        if "error" not in job and job["speaker_voice"] is not None:
+            try:
+                if voice_of(job["speaker_voice"]) is None:
+                    jobs[j] = {"error": f"speaker_voice '{job['speaker_voice']}' not found"}
+            except Exception as e:
+                jobs[j] = {"error": str(e), "error_type": type(e).__name__, "traceback": traceback.format_exc()}
+    chunks: Dict[int, Dict[int, torch.Tensor]] = {}
+    for call in calls:
+        rows = [r for r in call["rows"] if "error" not in jobs[r["job"]]]
+        if not rows:
+            continue
+        try:
+            ids, tmask = get_text_input_ids_and_mask([r["text"] for r in rows], max_length=768, device=device)
+            items = [dict(jobs[r["job"]]["item"], rng_seed=r["seed"]) for r in rows]
+            handles = [voice_of(jobs[r["job"]]["speaker_voice"]) for r in rows]
+            lat = sample_euler_items(model, None, None, ids, tmask, items, sequence_length=call["sequence_length"], speaker_kv=handles)
+            cut = find_flattening_points(lat)
+            for i, r in enumerate(rows):
+                audio = ae_decode(fish_ae, pca_state, lat[i:i + 1])
+                chunks.setdefault(r["job"], {})[r["chunk"]] = audio[0][..., : cut[i] * 2048]
+        except Exception as e:           # the call's jobs fail together; jobs of other calls go on
+            err = {"error": str(e), "error_type": type(e).__name__, "traceback": traceback.format_exc()}
+            for r in rows:
+                jobs[r["job"]] = dict(err)
+    out: List[Dict] = []
+    for j, job in enumerate(jobs):
+        if "error" in job:
+            out.append(job)
+            continue
+        try:
+            parts = [chunks[j][c] for c in range(len(job["pieces"]))]
+            if job["normalize_boundaries"] and len(parts) > 1:
+                audio = normalize_chunk_boundaries_device(parts, sample_rate=44100)
+            elif job["enable_crossfade"] and len(parts) > 1:
+                audio = crossfade_chunks_device(parts)
+            else:
+                audio = torch.cat(parts, dim=-1)
+            if audio.dim() == 1:
+                audio = audio.unsqueeze(0)
+            out.append({"audio": audio, "sample_rate": SAMPLE_RATE, "duration": audio.shape[-1] / SAMPLE_RATE, "chunks": len(parts),
+                        "seed": job["seed"], "text_length": job["text_length"]})
+        except Exception as e:
+            out.append({"error": str(e), "error_type": type(e).__name__, "traceback": traceback.format_exc()})
+    return out
+
+
 # --------------------------------------------------------------------------- the reference's entry points
 class _State:
     model = None

@@ -19,7 +19,7 @@ import torch
 
 from . import _lib as L
 from .autoencoder import DAC
-from .model import EchoDiT, KVHandle, timestep_embedding
+from .model import MAX_ITEMS, EchoDiT, KVHandle, timestep_embedding
 
 # --------------------------------------------------------------------------- text front end
 _REPLACEMENTS = (("…", "..."), ("’", "'"), ("”", '"'), ("\n", " "), (":", ","), (";", ","), ("—", ", "))
@@ -313,6 +313,126 @@ def sample_euler_cfg_independent_guidances(
         x_init = torch.randn((B, sequence_length, model.config.latent_size), device=device, dtype=torch.float32, generator=rng)
     return run_euler(model, x_init, steps, temb, cfg_scale_text, cfg_scale_speaker, truncation_factor, speaker_kv_scale,
                      speaker_kv_max_layers)
+
+
+# --------------------------------------------------------------------------- mixed batches: per-utterance parameters and voices
+# the reference's per-request sampler keys (handler.py:426-444 -> inference.py:428-447); num_steps is per call, see below
+ITEM_KEYS = ("num_steps", "cfg_scale_text", "cfg_scale_speaker", "cfg_min_t", "cfg_max_t", "truncation_factor", "rescale_k",
+             "rescale_sigma", "speaker_kv_scale", "speaker_kv_max_layers", "speaker_kv_min_t", "rng_seed")
+_KV_KEYS = ("speaker_kv_scale", "speaker_kv_max_layers", "speaker_kv_min_t")
+_SCHEDULE_KEYS = ("num_steps", "cfg_min_t", "cfg_max_t", "rescale_k", "rescale_sigma", "speaker_kv_scale", "speaker_kv_min_t")
+
+
+def check_sampler_items(items, batch: int, voice_slots: int, need_seed: bool = True) -> None:
+    """Host-side argument checks of `sample_euler_items` (no device work): `batch` text rows, `voice_slots` = batch size of the
+    speaker cache the call will use (item b reads slot b % voice_slots)."""
+    items = list(items)
+    if len(items) > MAX_ITEMS:
+        raise ValueError(f"at most {MAX_ITEMS} items per sampler call (3 rows per item in the CFG layout), got {len(items)}")
+    if not items or len(items) != batch:
+        raise ValueError(f"one item per text row expected: {batch} rows, {len(items)} items")
+    for b, it in enumerate(items):
+        unknown = set(it) - set(ITEM_KEYS)
+        missing = set(ITEM_KEYS) - set(it) - (set() if need_seed else {"rng_seed"})
+        if unknown or missing:
+            raise ValueError(f"item {b}: unknown keys {sorted(unknown)}, missing keys {sorted(missing)}")
+    steps = sorted({int(it["num_steps"]) for it in items})
+    if len(steps) != 1:
+        raise ValueError(f"all items of one sampler call share num_steps (it sets the t schedule and the launch count); got {steps}")
+    if voice_slots < 1 or batch % voice_slots:
+        raise ValueError(f"the speaker batch ({voice_slots}) must divide the number of items ({batch})")
+    for b in range(voice_slots, batch):
+        a = items[b % voice_slots]
+        if any(a[k] != items[b][k] for k in _KV_KEYS):
+            raise ValueError(f"items {b % voice_slots} and {b} share one voice slot but differ in their speaker-KV scaling parameters "
+                             f"{_KV_KEYS}: the slot's K / V exist once")
+
+
+def run_euler_items(model: EchoDiT, x_init: torch.Tensor, item_structs, num_steps: int, temb: torch.Tensor, start_pos: int = 0,
+                    use_latent: bool = False) -> torch.Tensor:
+    """One echo_sample_euler_items call: `item_structs` is a ctypes array of B EchoSamplerItem."""
+    B, S, _ = x_init.shape
+    p = L.EchoSamplerParams()
+    p.B, p.S, p.num_steps = B, S, int(num_steps)
+    p.start_pos, p.use_latent = int(start_pos), int(use_latent)
+    temb_dev = temb.to(model.device).contiguous()
+    p.temb = temb_dev.data_ptr()
+    x0 = x_init.to(model.device, torch.float32).contiguous()
+    out = torch.empty_like(x0)
+    L.check(model._lib.echo_sample_euler_items(model._ctx, C.byref(p), item_structs, x0.data_ptr(), out.data_ptr(), model._stream()), model._ctx)
+    return out
+
+
+def build_sampler_items(model: EchoDiT, items):
+    """items (dicts with ITEM_KEYS) -> (ctypes EchoSamplerItem array, temb, the step tables it points into).  `build_schedule` runs
+    once per distinct parameter set."""
+    schedules, keep = {}, []
+    arr = (L.EchoSamplerItem * len(items))()
+    temb = None
+    for b, it in enumerate(items):
+        key = tuple(it[k] for k in _SCHEDULE_KEYS)
+        if key not in schedules:
+            schedules[key] = build_schedule(model, int(it["num_steps"]), it["cfg_min_t"], it["cfg_max_t"], it["rescale_k"], it["rescale_sigma"],
+                                            it["speaker_kv_scale"], it["speaker_kv_min_t"])
+        steps, temb_b = schedules[key]
+        temb = temb_b if temb is None else temb
+        keep.append(steps)
+        a = arr[b]
+        a.cfg_scale_text, a.cfg_scale_speaker = float(it["cfg_scale_text"]), float(it["cfg_scale_speaker"])
+        a.has_truncation = int(it["truncation_factor"] is not None)
+        a.init_scale = 1.0 if it["truncation_factor"] is None else float(it["truncation_factor"])
+        a.kv_scale = 1.0 if it["speaker_kv_scale"] is None else float(it["speaker_kv_scale"])
+        a.kv_max_layers = -1 if it["speaker_kv_max_layers"] is None else int(it["speaker_kv_max_layers"])
+        a.steps = steps
+    return arr, temb, keep
+
+
+def _multiply_kv_cache_items(cache: KVHandle, scales, max_layers) -> None:
+    """reference inference.py:408-414 per utterance: item b's speaker K / V of layers < max_layers[b] (None: all) times scales[b]."""
+    m, n = cache.model, len(scales)
+    sc = (C.c_float * n)(*[float(s) for s in scales])
+    ml = (C.c_int32 * n)(*[-1 if v is None else int(v) for v in max_layers])
+    L.check(m._lib.echo_scale_speaker_kv_items(m._ctx, sc, ml, n, m._stream()), m._ctx)
+
+
+@torch.inference_mode()
+def sample_euler_items(model: EchoDiT, speaker_latent, speaker_mask, text_input_ids: torch.Tensor, text_mask: torch.Tensor, items, *,
+                       sequence_length: int | None = None, x_init: torch.Tensor | None = None, speaker_kv=None) -> torch.Tensor:
+    """reference inference.py:427-517 for B utterances that each bring their OWN request parameters: `items` is a list of B dicts
+    with exactly the reference's per-request keys (ITEM_KEYS); row b of the result is what `sample_euler_cfg_independent_guidances`
+    computes for row b with items[b].  Per call, not per item: `num_steps` (all items must agree: ValueError) and
+    `sequence_length`.  At most 32 items.  `speaker_kv`: one VoiceHandle shared by all rows, or a list of B batch-1 VoiceHandles
+    (one cached voice per row, `EchoDiT.bind_voices`); otherwise `speaker_latent` (B or 1 rows) is encoded.  Item b's noise is a
+    (1, S, latent) draw from items[b]["rng_seed"] - the noise the request would get alone - unless `x_init` is given."""
+    if sequence_length is None:
+        sequence_length = 640
+    items = [dict(it) for it in items]
+    B = int(text_input_ids.shape[0])
+    per_row_voices = isinstance(speaker_kv, (list, tuple))
+    if per_row_voices:
+        if len(speaker_kv) != B:
+            raise ValueError(f"one voice per text row expected: {B} rows, {len(speaker_kv)} voices")
+        slots = B
+    else:
+        slots = int(speaker_kv.batch) if speaker_kv is not None else int(speaker_latent.shape[0])
+    check_sampler_items(items, B, slots, need_seed=x_init is None)
+    device = model.device
+    arr, temb, _keep = build_sampler_items(model, items)
+    model.get_kv_cache_text(text_input_ids, text_mask)
+    if per_row_voices:
+        kv_spk = model.bind_voices(list(speaker_kv))
+    elif speaker_kv is not None:
+        kv_spk = model.bind_voice(speaker_kv)
+    else:
+        kv_spk = model.get_kv_cache_speaker(speaker_latent, speaker_mask)
+    if any(it["speaker_kv_scale"] is not None for it in items):
+        _multiply_kv_cache_items(kv_spk, [1.0 if it["speaker_kv_scale"] is None else it["speaker_kv_scale"] for it in items],
+                                 [it["speaker_kv_max_layers"] for it in items])
+    if x_init is None:
+        lz = model.config.latent_size
+        x_init = torch.cat([torch.randn((1, sequence_length, lz), device=device, dtype=torch.float32,
+                                        generator=torch.Generator(device=device).manual_seed(int(it["rng_seed"]))) for it in items], 0)
+    return run_euler_items(model, x_init, arr, int(items[0]["num_steps"]), temb)
 
 
 # --------------------------------------------------------------------------- pipelines (reference inference.py:308-388)

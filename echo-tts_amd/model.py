@@ -81,6 +81,20 @@ def mask_to_keys(mask: torch.Tensor) -> Tuple[List[int], Optional[torch.Tensor]]
     return nk, bias
 
 
+MAX_ITEMS = 32      # utterances per sampler call: 3 * B rows of the CFG layout <= 96 (engine MAXROWS)
+
+
+def pad_key_masks(masks: List[Optional[torch.Tensor]]) -> Optional[torch.Tensor]:
+    """Batch-1 key masks (1, T_i) of different widths -> one (n, max T) bool mask, False beyond each item's own width."""
+    if any(m is None for m in masks):
+        return None
+    width = max(int(m.shape[-1]) for m in masks)
+    out = torch.zeros((len(masks), width), dtype=torch.bool)
+    for i, m in enumerate(masks):
+        out[i, : m.shape[-1]] = m.detach().to("cpu", torch.bool).reshape(-1)
+    return out
+
+
 class KVHandle:
     """Stands in for the reference's List[Tuple[K, V]] caches: the tensors live inside the HIP context."""
 
@@ -286,6 +300,22 @@ class EchoDiT:
             raise L.EchoHipError("voice handle was closed")
         L.check(self._lib.echo_voice_bind(self._ctx, voice._ptr, self._stream()), self._ctx)
         return KVHandle(self, "speaker", voice.mask, voice.batch)
+
+    def bind_voices(self, voices: List[VoiceHandle]) -> KVHandle:
+        """One captured batch-1 voice per utterance of a mixed sampler call: together they become this context's speaker cache
+        of batch len(voices), without running the encoder.  The cache takes the longest voice's key count; every item keeps its
+        own, and its keys beyond it are zero-filled.  The handle's mask is the per-item key masks, padded with False."""
+        voices = list(voices)
+        if not 1 <= len(voices) <= MAX_ITEMS:
+            raise ValueError(f"bind_voices: 1..{MAX_ITEMS} voices expected, got {len(voices)}")
+        for v in voices:
+            if not v._ptr:
+                raise L.EchoHipError("voice handle was closed")
+            if v.batch != 1:
+                raise ValueError("bind_voices: every voice must have been captured with batch size 1")
+        ptrs = (C.c_void_p * len(voices))(*[v._ptr.value if isinstance(v._ptr, C.c_void_p) else v._ptr for v in voices])
+        L.check(self._lib.echo_voice_bind_items(self._ctx, ptrs, len(voices), self._stream()), self._ctx)
+        return KVHandle(self, "speaker", pad_key_masks([v.mask for v in voices]), len(voices))
 
     def workspace_bytes(self) -> int:
         return int(self._lib.echo_workspace_bytes(self._ctx))

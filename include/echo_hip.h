@@ -164,6 +164,39 @@ typedef struct {
  * latent_out (B,S,latent) fp32.  Text/speaker(/latent) KV must have been encoded on this ctx. */
 int echo_sample_euler(echo_ctx* ctx, const echo_sampler_params* p, const float* x_init, float* latent_out, void* stream);
 
+/* ---- mixed batches (added under ABI 8; additive: every declaration above keeps its layout and its bits) ----
+ * One sampler call whose utterances differ in every reference request parameter (handler.py:426-444, inference.py:428-447) and in
+ * their cached voice.  Two parameters stay per call because they set the launch geometry: num_steps and the sequence length S. */
+typedef struct {                 /* one utterance of a mixed call; host memory */
+  float cfg_scale_text, cfg_scale_speaker;
+  int has_truncation; float init_scale;      /* as in echo_sampler_params */
+  float kv_scale; int kv_max_layers;         /* used by THIS item's kv_unscale_after step: multiply by 1/kv_scale */
+  const echo_step* steps;        /* host, num_steps entries, this item's: has_cfg, dt, rescale coefficients, kv_unscale_after */
+} echo_sampler_item;
+
+/* inference.py:427-517 for B utterances with their own parameters: item b of latent_out is what the reference computes for item b
+ * with items[b].  `p` supplies B, S, num_steps, start_pos, use_latent and temb (all items share num_steps, hence the t schedule and
+ * one modulation table per step); its per-call scalar fields and p->steps are ignored.  The per-item step data goes to the device
+ * once, as a num_steps x B table, before the step loop; nothing is allocated or synchronised inside the loop once warm.
+ * Row set: a step runs the 3B-row CFG layout when ANY item has CFG at that step (B rows otherwise), which keeps the `row % B` KV
+ * addressing.  Cost: an item outside its CFG window still pays for its two un-conditional rows at such a step (they are computed and
+ * not used; compacting them away is not done).  An item without CFG at a step takes v_cond unchanged.  An item whose parameters equal
+ * those of a uniform echo_sample_euler call gets that call's bits.
+ * Fails (non-zero, text from echo_last_error) when B differs from the text cache's batch, 3B > 96 (more than 32 items), items or an
+ * item's steps is NULL, any item's steps[i].dt differs from item 0's, or utterances that share a voice slot (speaker cache of batch
+ * spkB < B, slot b % spkB) un-scale their speaker KV differently. */
+int echo_sample_euler_items(echo_ctx* ctx, const echo_sampler_params* p, const echo_sampler_item* items /* p->B entries */,
+                            const float* x_init, float* latent_out, void* stream);
+/* inference.py:408-414 per utterance: K, V and transposed V of item b's speaker cache, layers < max_layers_host[b] (-1: all), times
+ * scales_host[b], rounded as echo_scale_speaker_kv rounds.  An item with scale 1 keeps its bits untouched.  n is the speaker cache's
+ * batch size or a multiple of it; entries that share a voice slot (b % batch) must be equal, anything else fails. */
+int echo_scale_speaker_kv_items(echo_ctx* ctx, const float* scales_host, const int32_t* max_layers_host, int n, void* stream);
+/* n captured batch-1 voices (host array of n pointers) become this context's speaker cache of batch n: one voice per utterance without
+ * running the speaker encoder.  The cache takes the largest key count; item i keeps its own count, and its K / V rows and transposed-V
+ * columns beyond it are ZERO-FILLED (a masked key is multiplied by a zero probability; 0 x NaN from an uninitialised tail is not 0).
+ * A key bias is carried only if some voice has one; the others get 0 on their keys.  Same checks as echo_voice_bind. */
+int echo_voice_bind_items(echo_ctx* ctx, const echo_voice* const* voices, int n, void* stream);
+
 /* inference.py:226-229 ae_decode -> autoencoder.py:1128-1132 DAC.decode_zq, one batch item:
  * latent (T, latent_size) fp32 -> wav (T * hop) fp32.
  * ECHO_BF16 context (ABI 8): the PCA inverse is evaluated in fp32 and rounded to bf16 once (inference.py:227-229), the decoder runs in bf16 and the
