@@ -146,6 +146,9 @@ SIGNATURES = {
     "echo_voice_capture": (C.c_int, [vp, C.POINTER(vp), vp]),
     "echo_voice_bind": (C.c_int, [vp, vp, vp]),
     "echo_sample_euler_items": (C.c_int, [vp, C.POINTER(EchoSamplerParams), C.POINTER(EchoSamplerItem), vp, vp, vp]),
+    "echo_dit_forward_pos": (C.c_int, [vp, vp, vp, C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int,
+                                       C.POINTER(C.c_int32), C.POINTER(C.c_int32), vp, vp]),
+    "echo_sample_euler_items_pos": (C.c_int, [vp, C.POINTER(EchoSamplerParams), C.POINTER(EchoSamplerItem), C.POINTER(C.c_int32), vp, vp, vp]),
     "echo_scale_speaker_kv_items": (C.c_int, [vp, C.POINTER(C.c_float), C.POINTER(C.c_int32), C.c_int, vp]),
     "echo_voice_bind_items": (C.c_int, [vp, C.POINTER(vp), C.c_int, vp]),
     "echo_voice_bytes": (c_i64, [vp]),

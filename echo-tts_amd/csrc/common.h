@@ -142,6 +142,11 @@ struct GemmArgs {
   int qkv_gate_act;             // bf16 only: the gate section is stored as bf16(sigmoid_fast(bf16(acc))) - what the attention epilogue would
                                 // compute from it (AttnArgs.g_act = 1 then takes it as the multiplier): same bits, the exponentials ride in the GEMM tail
   float qk_eps;
+  // RoPE row of token m: rope[pos0 + m % rope_mod].  One start position per call: rope_mod = qkv_S, pos0 = start_pos, rope = the context's table.
+  // One start position PER UTTERANCE: rope = a per-call table of B * S rows gathered from the context's (row b * S + s holds
+  // position start[b] + s), rope_mod = B * S, pos0 = 0 - row r of the launch uses item r % B, so m % (B * S) is its row.  Every launch sets it
+  // (>= 1, checked by the launcher).  The V-transpose addressing keeps qkv_S.  (The field fills what was alignment padding: no offset moved.)
+  int rope_mod;
   const void* qk_w; const void* rope;
   void* vt; long vt_ld, vt_row_stride;
   // fp8 operands (gemm_pp_kernel only, activations/outputs stay bf16): A and W hold OCP e4m3 bytes, one fp32 scale per A row
@@ -201,6 +206,8 @@ template <typename T>
 hipError_t launch_headnorm_rope_nt(T* x, long ldx, long t_stride, int nt, int rows, int S, int H, const T* w, long w_stride,
                                    float eps, int do_norm, int rope_heads, const float2* rope, int pos0, int pos_mul,
                                    hipStream_t st);
+// out[b * S + s] = rope[start[b] + s] (rows of 64 float2): the per-call RoPE table of a forward with one start position per utterance
+hipError_t launch_rope_gather(const float2* rope, const int* start_dev, float2* out, int B, int S, hipStream_t st);
 template <typename T> hipError_t launch_embedding(const int* ids, const T* table, T* out, long ldo, int n, int D, hipStream_t st);
 template <typename T> hipError_t launch_silu(const T* x, T* y, long n, hipStream_t st);
 // bf16 rows -> OCP e4m3 bytes + per-row fp32 scale (amax / 448)

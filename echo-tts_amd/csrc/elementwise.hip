@@ -828,6 +828,25 @@ hipError_t launch_quant_rows_fp8(const void* x, long ldx, void* q, long ldq, flo
                      rows, K);
   return hipGetLastError();
 }
+// Per-utterance start positions: out[b * S + s] = rope[start[b] + s], one 512-byte row of 64 (cos, sin) pairs per token,
+// copied as 32 x 16 bytes.  The RoPE consumers then address the copy as m % (B * S) (GemmArgs.rope_mod) and read the very values a call
+// with the launch scalar start[b] reads.  The caller has checked 0 <= start[b] and start[b] + S <= rows of `rope`.
+__global__ void __launch_bounds__(256) rope_gather_kernel(const float4* __restrict__ rope, const int* __restrict__ start, float4* __restrict__ out,
+                                                          int B, int S) {
+  const long n = (long)B * S * 32;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+    const int row = (int)(i >> 5), j = (int)(i & 31);
+    const int b = row / S, s = row - b * S;
+    out[i] = rope[(long)(start[b] + s) * 32 + j];
+  }
+}
+hipError_t launch_rope_gather(const float2* rope, const int* start_dev, float2* out, int B, int S, hipStream_t st) {
+  if (!rope || !start_dev || !out || B < 1 || S < 1 || ((uintptr_t)rope & 15) || ((uintptr_t)out & 15)) return hipErrorInvalidValue;
+  const long vectors = (long)B * S * 32;
+  hipLaunchKernelGGL(rope_gather_kernel, dim3((unsigned)std::max(1L, std::min((vectors + 255) / 256, 2048L))), dim3(256), 0, st, (const float4*)rope,
+                     start_dev, (float4*)out, B, S);
+  return hipGetLastError();
+}
 hipError_t launch_mask_to_bias(const uint8_t* mask, float* bias, long n, hipStream_t st) {
   hipLaunchKernelGGL(mask_to_bias_kernel, grid1d(n), dim3(256), 0, st, mask, bias, n);
   return hipGetLastError();

@@ -206,6 +206,11 @@ struct EngineBase {
   virtual int sample_euler_items(const echo_sampler_params* p, const echo_sampler_item* items, const float* x0, float* out, hipStream_t st) = 0;
   virtual int scale_speaker_kv_items(const float* scales, const int32_t* max_layers, int n, hipStream_t st) = 0;
   virtual int voice_bind_items(const struct VoiceSnap* const* v, int n, hipStream_t st) = 0;
+  // per-utterance start positions (staggered streaming batches): item_pos is a host table of B entries
+  virtual int dit_forward_pos(const void* x, const void* temb, int n_t, const int32_t* row_t, int rows, int B, int S, const int32_t* item_pos,
+                              int use_latent, const int32_t* ton, const int32_t* son, float* v, hipStream_t st) = 0;
+  virtual int sample_euler_items_pos(const echo_sampler_params* p, const echo_sampler_item* items, const int32_t* item_pos, const float* x0,
+                                     float* out, hipStream_t st) = 0;
 };
 
 // Small host tables go to the device through a ring of pinned staging slots, without a host sync (the pattern of push_nkeys): a
@@ -291,13 +296,16 @@ struct Engine : EngineBase {
   DevBuf b_ex, b_exn, b_eqkvg, b_evt, b_eattn, b_eh, b_ein, b_enk;
   DevBuf b_dacA, b_dacB, b_dacC, b_dq, b_dscore, b_dvt, b_dmisc;
   DevBuf b_items, b_voice_tab;      // mixed batches: the sampler's (step, item) table | the voice gather's source table
+  DevBuf b_attn_keep;               // fp32 engine, per-utterance start positions: attention rows kept between the passes of attention_by_prefix_width
+  DevBuf b_pos_rope;                // per-utterance start positions: [POS_TAB_BYTES of int32 start positions | B * S gathered RoPE rows]
+  static constexpr size_t POS_TAB_BYTES = 512;
   HostStage stage_items;
   std::vector<DevBuf*> all_bufs() {
     return {&b_kv_text, &b_vt_text, &b_kv_spk, &b_vt_spk, &b_kv_lat, &b_vt_lat, &b_nkeys, &b_bias_text, &b_bias_spk,
             &b_xin, &b_x, &b_xn, &b_qkvg, &b_vt_self, &b_attn, &b_h, &b_vout, &b_scores, &b_biasrows, &b_segmeta, &b_attn_redo,
             &b_mod, &b_c1, &b_c2, &b_cond, &b_sc, &b_dn, &b_xstate, &b_vf32,
             &b_ex, &b_exn, &b_eqkvg, &b_evt, &b_eattn, &b_eh, &b_ein, &b_enk,
-            &b_dacA, &b_dacB, &b_dacC, &b_dq, &b_dscore, &b_dvt, &b_dmisc, &b_items, &b_voice_tab};
+            &b_dacA, &b_dacB, &b_dacC, &b_dq, &b_dscore, &b_dvt, &b_dmisc, &b_items, &b_voice_tab, &b_pos_rope, &b_attn_keep};
   }
   // text / speaker / latent cache geometry
   int kvB = 0;          // batch size of the text cache (= utterances per sampler call)
@@ -838,7 +846,7 @@ struct Engine : EngineBase {
       CK(launch_norm<T>(NORM_RMS_W, x, d, xn, d, M, d, cfg.norm_eps, e.an[i], nullptr, st));
       if (d % 256 == 0) {
         GemmArgs g = G(xn, d, e.wqkvg[i], d, qkvg, 4 * d, M, 4 * d, d);
-        g.qkv_mode = 1; g.qkv_D = d; g.qkv_S = Tn; g.rope_heads = H; g.pos0 = 0; g.qk_eps = cfg.norm_eps;
+        g.qkv_mode = 1; g.qkv_D = d; g.qkv_S = Tn; g.rope_mod = Tn; g.rope_heads = H; g.pos0 = 0; g.qk_eps = cfg.norm_eps;
         g.qk_w = e.qkn + (long)i * 2 * d; g.rope = rope; g.vt = vt; g.vt_ld = Tpad; g.vt_row_stride = (long)d * Tpad;
         CKI(run(g, st));
       } else {
@@ -1227,13 +1235,15 @@ struct Engine : EngineBase {
     return ECHO_OK;
   }
   // host_nk rows must already describe this forward (set_row_keys)
-  void set_row_keys(int rows, int B, int S, int start_pos, bool use_latent, const int32_t* ton, const int32_t* son) {
+  // item_pos (host, B entries; nullptr: every item starts at start_pos): row r sees the latent-prefix keys of item r % B's own position
+  void set_row_keys(int rows, int B, int S, int start_pos, bool use_latent, const int32_t* ton, const int32_t* son, const int32_t* item_pos = nullptr) {
     for (int r = 0; r < MAXROWS; ++r) {
       const int b = B > 0 ? r % B : 0;
       const bool in = r < rows;
       host_nk[0 * MAXROWS + r] = in ? S : 0;
       int nl = 0;
-      if (in && use_latent && lat_T > 0) nl = std::min(lat_T, (start_pos + cfg.speaker_patch_size - 1) / cfg.speaker_patch_size);
+      const int sp = item_pos ? item_pos[b] : start_pos;
+      if (in && use_latent && lat_T > 0) nl = std::min(lat_T, (sp + cfg.speaker_patch_size - 1) / cfg.speaker_patch_size);
       host_nk[1 * MAXROWS + r] = nl;
       host_nk[2 * MAXROWS + r] = (in && text_T > 0 && (!ton || ton[r])) ? text_nk[b] : 0;
       host_nk[3 * MAXROWS + r] = (in && spk_T > 0 && spkB > 0 && (!son || son[r])) ? spk_nk[b % spkB] : 0;
@@ -1247,15 +1257,19 @@ struct Engine : EngineBase {
   struct ModSeg { int row0, nrows; const T* mod; };
 
   // xin (rows*S, lat_pad) -> vout (rows*S, 128); modrow = this step's [2L][3][D] modulation table (or `segs`: per-row-range tables)
+  // item_pos != nullptr: one start position per utterance; prepare_item_pos() has put the gathered RoPE rows of exactly these positions
+  // into b_pos_rope (start_pos is then unused).  The RoPE consumers keep their arithmetic, base + m % modulus, on other arguments.
   int forward_rows(int rows, int B, int S, int start_pos, bool use_latent, const T* modrow, hipStream_t st,
-                   const std::vector<ModSeg>* segs_in = nullptr) {
+                   const std::vector<ModSeg>* segs_in = nullptr, const int32_t* item_pos = nullptr) {
     const std::vector<ModSeg> one = {ModSeg{0, rows, modrow}};
     const std::vector<ModSeg>& segs = segs_in ? *segs_in : one;
     const int D = cfg.model_size, L = cfg.num_layers, H = cfg.num_heads, F = cfg.intermediate_size, M = rows * S;
     const int Sp = (int)rup(S, 64);
     T *xin = b_xin.as<T>(), *x = b_x.as<T>(), *xn = b_xn.as<T>(), *qkvg = b_qkvg.as<T>(), *vts = b_vt_self.as<T>(),
       *ao = b_attn.as<T>(), *hh = b_h.as<T>(), *vout = b_vout.as<T>();
-    if (start_pos + S > rope_npos) return fail("rope table too short");
+    if (!item_pos && start_pos + S > rope_npos) return fail("rope table too short");
+    const float2* const rope_rows = item_pos ? (const float2*)((const char*)b_pos_rope.p + POS_TAB_BYTES) : rope;
+    const int rope_pos0 = item_pos ? 0 : start_pos, rope_mod = item_pos ? B * S : S;
     {
       GemmArgs g = G(xin, lat_pad, in_w, lat_pad, x, D, M, D, lat_pad);
       g.bias = in_b;
@@ -1286,14 +1300,14 @@ struct Engine : EngineBase {
       if (D % 256 == 0) {
         // one launch: projection + q/k head RMSNorm + half-head RoPE + transposed V (gemm.hip fused QKV epilogue)
         GemmArgs g = G(xn, D, wqkvg[l], D, qkvg, 4 * D, M, 4 * D, D);
-        g.qkv_mode = 1; g.qkv_D = D; g.qkv_S = S; g.rope_heads = H / 2; g.pos0 = start_pos; g.qk_eps = cfg.norm_eps;
-        g.qk_w = qkn + (long)l * 2 * D; g.rope = rope; g.vt = vts; g.vt_ld = Sp; g.vt_row_stride = (long)D * Sp;
+        g.qkv_mode = 1; g.qkv_D = D; g.qkv_S = S; g.rope_heads = H / 2; g.pos0 = rope_pos0; g.rope_mod = rope_mod; g.qk_eps = cfg.norm_eps;
+        g.qk_w = qkn + (long)l * 2 * D; g.rope = rope_rows; g.vt = vts; g.vt_ld = Sp; g.vt_row_stride = (long)D * Sp;
         g.qkv_gate_act = gate_act;       // bf16: the gate leaves the GEMM as bf16(sigmoid(gate)), the attention epilogue only multiplies
         if (fp8) CKI(to_fp8(g, q_wqkvg[l], s_wqkvg[l], st, nq1));
         CKI(run(g, st));
       } else {
         CKI(run(G(xn, D, wqkvg[l], D, qkvg, 4 * D, M, 4 * D, D), st));
-        CK(launch_headnorm_rope_nt<T>(qkvg, 4 * D, D, 2, M, S, H, qkn + (long)l * 2 * D, D, cfg.norm_eps, 1, H / 2, rope, start_pos, 1, st));
+        CK(launch_headnorm_rope_nt<T>(qkvg, 4 * D, D, 2, M, rope_mod, H, qkn + (long)l * 2 * D, D, cfg.norm_eps, 1, H / 2, rope_rows, rope_pos0, 1, st));
         CK(launch_transpose_heads<T>(qkvg + 2 * D, 4 * D, vts, Sp, (long)D * Sp, rows, S, H, 128, st));
       }
       SegDesc sg[4];
@@ -1322,6 +1336,8 @@ struct Engine : EngineBase {
         CKI(fp8_reserve(M, std::max(D, F)));
         CK(b_h8.reserve((size_t)(M + 256) * F));
         CKI(attention(qkvg, 4 * D, qkvg + 3 * D, 4 * D, ao, D, rows, S, H, sg, 4, false, st, b_q8.as<uint8_t>(), D, 1.0f / fp8_static[2 * l], gate_act));
+      } else if (!Num<T>::is_bf16 && item_pos && max_lat > 0) {
+        CKI(attention_by_prefix_width(qkvg, D, ao, rows, S, H, sg, gate_act, st));
       } else {
         CKI(attention(qkvg, 4 * D, qkvg + 3 * D, 4 * D, ao, D, rows, S, H, sg, 4, false, st, nullptr, 0, 0.f, gate_act));
       }
@@ -1370,6 +1386,34 @@ struct Engine : EngineBase {
     return ECHO_OK;
   }
 
+  // fp32 parity engine, one start position per utterance.  attention_f32 lays the scores of a row out as the concatenated columns of the
+  // ACTIVE segments, the latent-prefix segment rup(max key count of the call, 32) columns wide, and sums a softmax row in column order: a
+  // row's bits depend on the widest prefix among its batch-mates.  So that an item at position p keeps the bits of a uniform call at p, the
+  // rows are grouped by THEIR OWN prefix width rup(nl, 32) (0: no latent segment at all); one attention pass per width computes every row
+  // with that layout and the rows of that width are kept.  One width (the usual case): one pass, as before.  The bf16 attention kernel
+  // walks the segments per row and has no such dependence.
+  int attention_by_prefix_width(T* qkvg, int D, T* ao, int rows, int S, int H, const SegDesc* sg_in, int gate_act, hipStream_t st) {
+    std::map<int, int> width_maxk;      // width class -> largest key count in it
+    for (int r = 0; r < rows; ++r) {
+      const int nl = host_nk[1 * MAXROWS + r];
+      int& mk = width_maxk[(int)rup(nl, 32)];
+      mk = std::max(mk, nl);
+    }
+    SegDesc sg[4] = {sg_in[0], sg_in[1], sg_in[2], sg_in[3]};
+    if (width_maxk.size() == 1) return attention(qkvg, 4 * D, qkvg + 3 * D, 4 * D, ao, D, rows, S, H, sg, 4, false, st, nullptr, 0, 0.f, gate_act);
+    const size_t row_bytes = (size_t)S * D * sizeof(T);
+    CK(b_attn_keep.reserve((size_t)rows * row_bytes));
+    for (const auto& wc : width_maxk) {
+      sg[1].maxk = wc.second;
+      CKI(attention(qkvg, 4 * D, qkvg + 3 * D, 4 * D, ao, D, rows, S, H, sg, 4, false, st, nullptr, 0, 0.f, gate_act));
+      for (int r = 0; r < rows; ++r)
+        if ((int)rup(host_nk[1 * MAXROWS + r], 32) == wc.first)
+          CK(hipMemcpyAsync((char*)b_attn_keep.p + r * row_bytes, (const char*)ao + r * row_bytes, row_bytes, hipMemcpyDeviceToDevice, st));
+    }
+    CK(hipMemcpyAsync(ao, b_attn_keep.p, (size_t)rows * row_bytes, hipMemcpyDeviceToDevice, st));
+    return ECHO_OK;
+  }
+
   // modulation tables for N timesteps (model.py:583, 70-74, 79-81): mod[n][2L][3][D]
   int compute_mod(const T* temb, int N, hipStream_t st) {
     const int D = cfg.model_size, L = cfg.num_layers, E = cfg.timestep_embed_size, R = cfg.adaln_rank;
@@ -1407,9 +1451,40 @@ struct Engine : EngineBase {
     return ECHO_OK;
   }
 
-  // temb: (n_t, E) timestep embeddings; row_t (host, rows) = which of them each row uses (nullptr: all rows use embedding 0)
+  // Per-utterance start positions (inference_blockwise.py:59-121 run for B streams that stand at different blocks).  Checks the table, sends
+  // it to the device through the staging ring and gathers the B * S RoPE rows the call's forwards read: once per call, in front of the
+  // step loop; no allocation and no synchronisation once the geometry is warm.
+  int prepare_item_pos(const int32_t* item_pos, int B, int S, hipStream_t st) {
+    if (!item_pos) return fail("per-utterance start positions: null position table");
+    if (B < 1 || 3 * B > MAXROWS || (size_t)B * sizeof(int32_t) > POS_TAB_BYTES) return fail("per-utterance start positions: at most 32 items per call (3 B <= 96 rows)");
+    if (S < 1) return fail("per-utterance start positions: bad sequence length");
+    if (!rope) return fail("rope table not set");
+    for (int b = 0; b < B; ++b) {
+      if (item_pos[b] < 0) return fail("per-utterance start positions: a start position is negative");
+      if ((long)item_pos[b] + S > rope_npos) return fail("per-utterance start positions: a start position plus S runs past the rope table (rope table too short)");
+    }
+    CK(b_pos_rope.reserve(POS_TAB_BYTES + (size_t)B * S * 64 * sizeof(float2)));
+    CK(stage_items.push(item_pos, (size_t)B * sizeof(int32_t), b_pos_rope.p, st));
+    CK(launch_rope_gather(rope, b_pos_rope.as<int>(), (float2*)((char*)b_pos_rope.p + POS_TAB_BYTES), B, S, st));
+    return ECHO_OK;
+  }
+
   int dit_forward(const void* x, const void* temb, int n_t, const int32_t* row_t, int rows, int B, int S, int start_pos, int use_latent,
                   const int32_t* ton, const int32_t* son, float* v, hipStream_t st) override {
+    return dit_forward_any(x, temb, n_t, row_t, rows, B, S, start_pos, nullptr, use_latent, ton, son, v, st);
+  }
+  int dit_forward_pos(const void* x, const void* temb, int n_t, const int32_t* row_t, int rows, int B, int S, const int32_t* item_pos,
+                      int use_latent, const int32_t* ton, const int32_t* son, float* v, hipStream_t st) override {
+    if (!dit_ready) return fail("echo_finalize_dit was not called");
+    if (!item_pos) return fail("per-utterance start positions: null position table");
+    if (B < 1 || 3 * B > MAXROWS) return fail("per-utterance start positions: at most 32 items per call (3 B <= 96 rows)");
+    if (rows < 1 || rows > MAXROWS || rows % B || B != kvB) return fail("bad rows/B");
+    CKI(prepare_item_pos(item_pos, B, S, st));
+    return dit_forward_any(x, temb, n_t, row_t, rows, B, S, 0, item_pos, use_latent, ton, son, v, st);
+  }
+  // temb: (n_t, E) timestep embeddings; row_t (host, rows) = which of them each row uses (nullptr: all rows use embedding 0)
+  int dit_forward_any(const void* x, const void* temb, int n_t, const int32_t* row_t, int rows, int B, int S, int start_pos, const int32_t* item_pos,
+                      int use_latent, const int32_t* ton, const int32_t* son, float* v, hipStream_t st) {
     if (!dit_ready) return fail("echo_finalize_dit was not called");
     if (rows < 1 || rows > MAXROWS || B < 1 || rows % B || B != kvB) return fail("bad rows/B");
     if (spk_T > 0 && (spkB < 1 || kvB % spkB)) return fail("the speaker cache's batch size must divide the text cache's");
@@ -1426,12 +1501,12 @@ struct Engine : EngineBase {
       if (!segs.empty() && segs.back().mod == mod) ++segs.back().nrows;
       else segs.push_back(ModSeg{r, 1, mod});
     }
-    set_row_keys(rows, B, S, start_pos, use_latent != 0, ton, son);
+    set_row_keys(rows, B, S, start_pos, use_latent != 0, ton, son, item_pos);
     CKI(push_nkeys(st));
     // x (M, latent) -> xin (M, lat_pad) zero padded
     CK(hipMemcpy2DAsync(b_xin.p, lat_pad * sizeof(T), x, cfg.latent_size * sizeof(T), cfg.latent_size * sizeof(T), M,
                         hipMemcpyDeviceToDevice, st));
-    CKI(forward_rows(rows, B, S, start_pos, use_latent != 0, b_mod.as<T>(), st, &segs));
+    CKI(forward_rows(rows, B, S, start_pos, use_latent != 0, b_mod.as<T>(), st, &segs, item_pos));
     CK(launch_convert_to_f32<T>(b_vout.as<T>(), 128, v, cfg.latent_size, M, cfg.latent_size, st));
     return ECHO_OK;
   }
@@ -1495,6 +1570,17 @@ struct Engine : EngineBase {
   // item brings its own scales, truncation, KV scale and step table.  A step runs the 3B-row CFG layout when ANY item has CFG at
   // it (the `row % B` KV addressing stays), so items outside their window ride along in the un-conditional rows.
   int sample_euler_items(const echo_sampler_params* p, const echo_sampler_item* items, const float* x0, float* out, hipStream_t st) override {
+    return sample_euler_items_any(p, items, nullptr, false, x0, out, st);
+  }
+  int sample_euler_items_pos(const echo_sampler_params* p, const echo_sampler_item* items, const int32_t* item_pos, const float* x0, float* out,
+                             hipStream_t st) override {
+    if (!item_pos) return fail("per-utterance start positions: null position table");
+    if (p && (p->B < 1 || 3 * p->B > MAXROWS)) return fail("per-utterance start positions: at most 32 items per call (3 B <= 96 rows)");
+    return sample_euler_items_any(p, items, item_pos, true, x0, out, st);
+  }
+  // with_pos: p->start_pos is ignored, item b starts at item_pos[b] (host, B entries)
+  int sample_euler_items_any(const echo_sampler_params* p, const echo_sampler_item* items, const int32_t* item_pos, bool with_pos, const float* x0,
+                             float* out, hipStream_t st) {
     if (!dit_ready) return fail("echo_finalize_dit was not called");
     if (!p || !items) return fail("mixed sampler call: null params / items");
     const int B = p->B, S = p->S, N = p->num_steps, Lz = cfg.latent_size;
@@ -1534,6 +1620,7 @@ struct Engine : EngineBase {
       memset(&unscale[i], 0, sizeof(KvItemScales));
       if (has_unscale[i]) CKI(kv_slot_scales(us.data(), ul.data(), B, unscale[i]));
     }
+    if (with_pos) CKI(prepare_item_pos(item_pos, B, S, st));      // refuses a null table / a position past the rope table before any work is queued
     const int rows3 = 3 * B;
     CKI(reserve_dit_ws(rows3 * S, rows3, S));
     CK(b_xstate.reserve((size_t)B * S * Lz * sizeof(float)));
@@ -1557,7 +1644,7 @@ struct Engine : EngineBase {
     if (profiling) CK(hipEventRecord(ev[1], st));
     std::vector<int32_t> ton(rows3, 1), son(rows3, 1);
     for (int b = 0; b < B; ++b) { ton[B + b] = 0; son[2 * B + b] = 0; }
-    set_row_keys(rows3, B, S, p->start_pos, p->use_latent != 0, ton.data(), son.data());
+    set_row_keys(rows3, B, S, p->start_pos, p->use_latent != 0, ton.data(), son.data(), with_pos ? item_pos : nullptr);
     CKI(push_nkeys(st));
     const long modstride = (long)2 * cfg.num_layers * 3 * cfg.model_size;
     EulerItemsArgs e;
@@ -1569,7 +1656,7 @@ struct Engine : EngineBase {
     CK(launch_euler_items<T>(e, st));
     for (int i = 0; i < N; ++i) {
       const int rows = any_cfg[i] ? rows3 : B;
-      CKI(forward_rows(rows, B, S, p->start_pos, p->use_latent != 0, b_mod.as<T>() + (long)i * modstride, st));
+      CKI(forward_rows(rows, B, S, p->start_pos, p->use_latent != 0, b_mod.as<T>() + (long)i * modstride, st, nullptr, with_pos ? item_pos : nullptr));
       if (has_unscale[i]) CKI(launch_kv_slot_scales(unscale[i], st));
       e.init = 0;
       e.R = any_cfg[i] ? 3 : 1;
@@ -2467,6 +2554,14 @@ int echo_voice_bind_items(echo_ctx* ctx, const echo_voice* const* voices, int n,
   }
   return ctx->eng->voice_bind_items(vs, n, (hipStream_t)stream);
 }
+int echo_dit_forward_pos(echo_ctx* ctx, const void* x, const void* temb, int n_t, const int32_t* row_t, int rows, int B, int S,
+                         const int32_t* item_start_pos, int use_latent, const int32_t* ton, const int32_t* son, float* v_out, void* stream) {
+  return ctx ? ctx->eng->dit_forward_pos(x, temb, n_t, row_t, rows, B, S, item_start_pos, use_latent, ton, son, v_out, (hipStream_t)stream) : ECHO_ERR;
+}
+int echo_sample_euler_items_pos(echo_ctx* ctx, const echo_sampler_params* p, const echo_sampler_item* items, const int32_t* item_start_pos,
+                                const float* x_init, float* latent_out, void* stream) {
+  return ctx ? ctx->eng->sample_euler_items_pos(p, items, item_start_pos, x_init, latent_out, (hipStream_t)stream) : ECHO_ERR;
+}
 int echo_scale_speaker_kv_items(echo_ctx* ctx, const float* scales_host, const int32_t* max_layers_host, int n, void* stream) {
   return ctx ? ctx->eng->scale_speaker_kv_items(scales_host, max_layers_host, n, (hipStream_t)stream) : ECHO_ERR;
 }
@@ -2529,7 +2624,7 @@ int echo_op_gemm(int dtype, const echo_gemm_desc* d, void* stream) {
   g.cfg = d->cfg; g.ksplit = d->ksplit; g.ws = d->ws; g.ws_bytes = d->ws_bytes; g.split3 = d->split3; g.w_presplit = d->split3 ? d->w_presplit : 0;
   g.fp8 = d->fp8; g.a_scale = d->a_scale; g.w_scale = d->w_scale;
   g.a_scale_const = d->a_scale_const; g.c8 = d->c8; g.c8_ld = d->c8_ld; g.c8_inv = d->c8_inv; g.qkv_gate_act = d->qkv_gate_act;
-  g.qkv_mode = d->qkv_mode; g.qkv_D = d->qkv_D; g.qkv_S = d->qkv_S; g.rope_heads = d->rope_heads; g.pos0 = d->pos0; g.qk_eps = d->qk_eps;
+  g.qkv_mode = d->qkv_mode; g.qkv_D = d->qkv_D; g.qkv_S = d->qkv_S; g.rope_mod = d->qkv_S; g.rope_heads = d->rope_heads; g.pos0 = d->pos0; g.qk_eps = d->qk_eps;
   g.qk_w = d->qk_w; g.rope = d->rope; g.vt = d->vt; g.vt_ld = d->vt_ld; g.vt_row_stride = d->vt_row_stride;
   if (dtype == ECHO_BF16 && g.snake_alpha && g.C2) {
     // bf16 conv forms take the branch-free conv tails at the 96- / 192-column tiles, as in the engine: they need a sink for their idle threads' stores

@@ -146,7 +146,7 @@ __device__ __forceinline__ void gemm_tail8(const GemmArgs& p, int m, int n0, flo
 // store, column scale + residual: wo / w2, and the generic bias / activation form), TAIL_QKV = the fused QKV(G) tail only, TAIL_ALL = everything
 // (split-K and the diagnostic builds).  The launcher picks the instantiation from the arguments.
 typedef const __attribute__((address_space(4))) GemmArgs* kargs_t;      // the kernel's argument block in the kernarg segment
-enum { TAIL_ALL = 0, TAIL_ROWS = 1, TAIL_QKV = 2, TAIL_FAST = 3, TAIL_FASTR = 4 };      // TAIL_FAST: y = T(acc) only (plain store); TAIL_FASTR: y = T(T(T(acc) * colscale) + residual) (wo, w2)
+enum { TAIL_ALL = 0, TAIL_ROWS = 1, TAIL_QKV = 2, TAIL_FAST = 3, TAIL_FASTR = 4, TAIL_QKVP = 5 };      // TAIL_FAST: y = T(acc) only (plain store); TAIL_FASTR: y = T(T(T(acc) * colscale) + residual) (wo, w2)
 template <bool SWIGLU, int DIAG = 0, int LEAD = PP_LEAD, bool FP8 = false, int TAIL = TAIL_ALL>
 __global__ void __launch_bounds__(512, 2) gemm_pp_kernel(const GemmArgs p) {
   typedef bf16_t T;
@@ -416,7 +416,7 @@ __global__ void __launch_bounds__(512, 2) gemm_pp_kernel(const GemmArgs p) {
     // nothing reads them during the epilogue, so hipcc spilled them there and reloaded them in front of the K loop - with the wait for that
     // reload INSIDE the steady loop (fp8 QKV instantiation: a vmcnt(0) per K-tile, the LDS-DMA ring drained every time).  Redefined at the tile
     // top, they are not live across the epilogue at all.
-    if constexpr (FP8 && TAIL == TAIL_QKV) set_stage_tile(v_stage);      // (this instantiation only: in the others the register allocation came out worse with it)
+    if constexpr (FP8 && (TAIL == TAIL_QKV || TAIL == TAIL_QKVP)) set_stage_tile(v_stage);      // (this instantiation only: in the others the register allocation came out worse with it)
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -451,6 +451,9 @@ __global__ void __launch_bounds__(512, 2) gemm_pp_kernel(const GemmArgs p) {
     // accumulators while everything else is still live: this instantiation spilled 49 VGPRs); the tails that compute in the accumulator layout
     // (SwiGLU pairs, head norm / RoPE) and the generic ones dequantise there.
     constexpr bool IS_FAST = TAIL == TAIL_FAST || TAIL == TAIL_FASTR;
+    // TAIL_QKVP: the fused QKV(G) tail whose RoPE row is rope[pos0 + m % rope_mod] instead of rope[pos0 + m % qkv_S] (one start position per
+    // utterance, GemmArgs.rope_mod).  An instantiation of its own: TAIL_QKV and TAIL_ALL keep their code and registers.
+    constexpr bool IS_QKV = TAIL == TAIL_QKV || TAIL == TAIL_QKVP;
     constexpr bool ROWDEQ = FP8 && IS_FAST;
     if constexpr (FP8 && !ROWDEQ) {
       // dequantise in the accumulator layout: lane_e holds C[m_base + 16 i + fr_e][n_base + 16 jn + 4 fg_e + r]
@@ -523,7 +526,7 @@ __global__ void __launch_bounds__(512, 2) gemm_pp_kernel(const GemmArgs p) {
           }
         });
       }
-    } else if ((TAIL == TAIL_ALL || TAIL == TAIL_QKV) && (TAIL == TAIL_QKV || p.qkv_mode)) {
+    } else if ((TAIL == TAIL_ALL || IS_QKV) && (IS_QKV || p.qkv_mode)) {
       // Fused QKV(G) tail.  Like the fast tail below it comes in BRANCH-FREE forms, one per (section kind, interior | edge tile), picked by
       // wave-uniform branches OUTSIDE the code that touches memory: a load or store behind a branch - the former `if (sec < 2)` / `if (do_rope)`
       // around the rope / norm-weight requests, the per-lane `if (m < M)` around every store - leaves hipcc's wait-count pass guessing at the
@@ -602,7 +605,7 @@ __global__ void __launch_bounds__(512, 2) gemm_pp_kernel(const GemmArgs p) {
             for (int j = 0; j < 4; ++j) w4p[j] = *(const uint2*)(wp + 16 * j);
             if constexpr (ROPE) {
               const int m = m_base + 16 * i_ + fr_e;
-              const int pos = pk->pos0 + m % pk->qkv_S;
+              const int pos = pk->pos0 + m % (TAIL == TAIL_QKVP ? pk->rope_mod : pk->qkv_S);
               const float4* rp = (const float4*)((const float2*)pk->rope + (long)pos * 64) + fg_e;     // pairs 8 jn + 2 fg_e, + 1
 #pragma unroll
               for (int j = 0; j < 4; ++j) cs[j] = rp[4 * (4 * h_ + j)];
@@ -681,7 +684,7 @@ __global__ void __launch_bounds__(512, 2) gemm_pp_kernel(const GemmArgs p) {
           if (full) qkg(IC<0>{}, IC<0>{}, IC<0>{}, IC<1>{}); else qkg(IC<0>{}, IC<0>{}, IC<0>{}, IC<0>{});
         }
       }
-    } else if (TAIL == TAIL_QKV) {
+    } else if (IS_QKV) {
       // (this instantiation is only launched with qkv_mode set)
     } else if (IS_FAST || (p.acc_scale == 1.0f && !p.bias && p.div == 0.0f && p.act == 0 && !p.vec_mod && DIAG != 7)) {
       // fast path of the big EchoDiT linears: y = T(acc) [* colscale] [+ residual].  Fully unrolled (static accumulator
@@ -888,7 +891,7 @@ hipError_t launch_pp(const GemmArgs& g, hipStream_t st) {
   if constexpr (DIAG == 0 && LEAD == PP_LEAD && !SW) {
     static const bool split = getenv("ECHO_PP_TAILS") ? atoi(getenv("ECHO_PP_TAILS")) != 0 : true;
     if (split && g.ksplit <= 1) {
-      if (g.qkv_mode) return launch_pp_tail<SW, DIAG, LEAD, FP8, TAIL_QKV>(g, st);
+      if (g.qkv_mode) return g.rope_mod != g.qkv_S ? launch_pp_tail<SW, DIAG, LEAD, FP8, TAIL_QKVP>(g, st) : launch_pp_tail<SW, DIAG, LEAD, FP8, TAIL_QKV>(g, st);
       if (g.acc_scale == 1.0f && !g.bias && g.div == 0.0f && g.act == 0 && !g.vec_mod) {
         if (!(g.N & 255)) {      // the branch-free edge form of these two needs whole tile columns
           if (!g.colscale && !g.res) return launch_pp_tail<SW, DIAG, LEAD, FP8, TAIL_FAST>(g, st);
@@ -898,6 +901,7 @@ hipError_t launch_pp(const GemmArgs& g, hipStream_t st) {
       return launch_pp_tail<SW, DIAG, LEAD, FP8, TAIL_ROWS>(g, st);
     }
   }
+  if (g.qkv_mode && g.rope_mod != g.qkv_S) return hipErrorInvalidValue;      // the RoPE-modulus form exists as the production tail-specialised build only
   return launch_pp_tail<SW, DIAG, LEAD, FP8, TAIL_ALL>(g, st);
 }
 

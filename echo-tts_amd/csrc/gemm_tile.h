@@ -40,7 +40,9 @@ struct EpiProf { unsigned long long t_bar1 = 0, t_put = 0, t_bar2 = 0, t_rw = 0;
 #define EPI_STAMP(var) do { if constexpr (PROF) { const unsigned long long n__ = __builtin_amdgcn_s_memtime(); prof->var += n__ - last__; last__ = n__; } } while (0)
 
 // NTAIL: 0 = every tail, 1 = the row-layout tails only (generic / SwiGLU): instantiations launched without split-K and without the fused QKV tail
-// do not carry those branches (and their registers) at all - see gemm_pp_kernel's TAIL
+// do not carry those branches (and their registers) at all - see gemm_pp_kernel's TAIL; 2..5 = the conv tails; 6 = the fused QKV tail alone, with the
+// RoPE row rope[pos0 + m % rope_mod] instead of rope[pos0 + m % qkv_S] (one start position per utterance, GemmArgs.rope_mod) - an
+// instantiation of its own, so that NTAIL 0 keeps its code and registers
 template <typename T, bool SWIGLU, int BM, int BN, int NT, bool DRAIN, bool PROF = false, int NTAIL = 0, typename PutFn>
 __device__ __forceinline__ void gemm_epilogue(const GemmArgs& p, float* slab, int tid, int tile_m, int tile_n, int tiles_m, int zo, int zi,
                                               long c_z, int split, PutFn put, EpiProf* prof = nullptr) {
@@ -65,7 +67,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& p, float* slab, in
   const int g_chunk = tid % CPR, g_r0 = tid / CPR;
   const int g_n0 = tile_n * BN + g_chunk * 4;
   const bool g_col_ok = tid < NTA && g_n0 < p.N;
-  const bool generic = NTAIL >= 1 ? !SWIGLU : (!(p.ksplit > 1) && !SWIGLU && !p.qkv_mode);
+  const bool generic = NTAIL == 6 ? false : NTAIL >= 1 ? !SWIGLU : (!(p.ksplit > 1) && !SWIGLU && !p.qkv_mode);
   float rs_next[ITER][4];
 #pragma unroll
   for (int k = 0; k < ITER; ++k)
@@ -89,7 +91,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& p, float* slab, in
       Vec4<T>::unpack(*(const typename Vec4<T>::raw*)((const T*)p.res + zo * p.res_bo + zi * p.res_bi + (long)(mc < p.M ? mc : p.M - 1) * p.ldres + nc), rs_next[k]);
     }
   };
-  if constexpr (NTAIL >= 2) {
+  if constexpr (NTAIL >= 2 && NTAIL <= 5) {
     const int nc = g_n0 + 3 < p.N ? g_n0 : p.N - 4;
     const int nv = p.vec_mod ? nc % p.vec_mod : nc;
     const long bo = zo * p.bias_bo + zi * p.bias_bi;
@@ -143,7 +145,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& p, float* slab, in
         const f32x4 b4 = *(const f32x4*)(slab + slab_pos<CPR>(ml, b * 8 + 4 + q) * 4);
         swiglu_tail<T>(p, m, j0, a4, b4, C);
       }
-    } else if (NTAIL == 0 && p.qkv_mode) {
+    } else if (NTAIL == 6 || (NTAIL == 0 && p.qkv_mode)) {
       const int D = p.qkv_D;
       const int sec = (tile_n * BN) / D;           // the whole tile lies in one of q | k | v | gate (D % BN == 0)
       if (sec == 2) {
@@ -191,7 +193,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& p, float* slab, in
             for (int i = 0; i < 4; ++i)
               y[i] = Num<T>::rnd(__fmul_rn(__fmul_rn(y[i], rs), vec_at<T>(p.qk_w, (long)sec * D + nd + i)));
             if ((nd >> 7) < p.rope_heads) {
-              const int pos = p.pos0 + m % p.qkv_S;
+              const int pos = p.pos0 + m % (NTAIL == 6 ? p.rope_mod : p.qkv_S);
               const float2* rp = (const float2*)p.rope + (long)pos * 64 + ((nd & 127) >> 1);
 #pragma unroll
               for (int pr = 0; pr < 2; ++pr) {
@@ -209,7 +211,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& p, float* slab, in
           if (m < p.M && n0 < p.N) *(typename Vec4<T>::raw*)(C + (long)m * p.ldc + n0) = Vec4<T>::pack(y);
         }
       }
-    } else if constexpr (NTAIL >= 2) {
+    } else if constexpr (NTAIL >= 2 && NTAIL <= 5) {
       // ---- branch-free conv tail (the Fish S1-DAC decoder's Conv1d / ConvTranspose1d launches): y = acc + bias [+ residual],
       // main output [optional], second output snake(y).  NTAIL = 2 + RES + 2 MAIN.  Nothing that touches memory sits behind a branch:
       // the residual rows are loaded from clamped addresses, the stores of threads without a row (beyond the tile's last full row of
@@ -526,6 +528,10 @@ hipError_t launch_cfg(const GemmArgs& g, hipStream_t st) {
       return g.store_main ? launch_cfg_tail<T, SW, CF, SPLIT3, 4>(g, st) : launch_cfg_tail<T, SW, CF, SPLIT3, 2>(g, st);
     }
   }
+  if constexpr (!SW && !SPLIT3 && (CF::BN == 128 || CF::BN == 256)) {      // cfg 0-4: the tiles the fused QKV tail is launched with
+    if (g.qkv_mode && g.rope_mod != g.qkv_S) return g.ksplit <= 1 ? launch_cfg_tail<T, SW, CF, SPLIT3, 6>(g, st) : hipErrorInvalidValue;
+  }
+  if (g.qkv_mode && g.rope_mod != g.qkv_S) return hipErrorInvalidValue;
   if (split && g.ksplit <= 1 && !g.qkv_mode) return launch_cfg_tail<T, SW, CF, SPLIT3, 1>(g, st);
   return launch_cfg_tail<T, SW, CF, SPLIT3, 0>(g, st);
 }
@@ -604,7 +610,7 @@ hipError_t launch_gemm_nt(const GemmArgs& g, hipStream_t st) {
       g.taps < 1 || g.nbatch < 1 || g.nbi < 1 || (g.lda % (16 / (int)sizeof(T))) || (g.ldw % (16 / (int)sizeof(T))) ||
       (g.ldc & 3) || g.cfg < 0 || (g.cfg >= gemm_num_cfgs() && (g.cfg < 101 || g.cfg > 111)))
     return hipErrorInvalidValue;
-  if (g.qkv_mode && (g.ksplit > 1 || g.swiglu || g.nbatch != 1 || g.qkv_D % 256 || !g.vt || !g.qk_w || !g.rope || g.qkv_S < 1))
+  if (g.qkv_mode && (g.ksplit > 1 || g.swiglu || g.nbatch != 1 || g.qkv_D % 256 || !g.vt || !g.qk_w || !g.rope || g.qkv_S < 1 || g.rope_mod < 1))
     return hipErrorInvalidValue;
   if (g.ksplit > 1) {
     if (g.nbatch != 1 || !g.ws || g.ksplit > (g.K / KE) * g.taps) return hipErrorInvalidValue;

@@ -19,7 +19,7 @@ import torch
 
 from . import _lib as L
 from .autoencoder import DAC
-from .model import MAX_ITEMS, EchoDiT, KVHandle, timestep_embedding
+from .model import MAX_ITEMS, EchoDiT, KVHandle, item_start_positions, timestep_embedding
 
 # --------------------------------------------------------------------------- text front end
 _REPLACEMENTS = (("…", "..."), ("’", "'"), ("”", '"'), ("\n", " "), (":", ","), (";", ","), ("—", ", "))
@@ -348,17 +348,23 @@ def check_sampler_items(items, batch: int, voice_slots: int, need_seed: bool = T
                              f"{_KV_KEYS}: the slot's K / V exist once")
 
 
-def run_euler_items(model: EchoDiT, x_init: torch.Tensor, item_structs, num_steps: int, temb: torch.Tensor, start_pos: int = 0,
+def run_euler_items(model: EchoDiT, x_init: torch.Tensor, item_structs, num_steps: int, temb: torch.Tensor, start_pos=0,
                     use_latent: bool = False) -> torch.Tensor:
-    """One echo_sample_euler_items call: `item_structs` is a ctypes array of B EchoSamplerItem."""
+    """One echo_sample_euler_items call: `item_structs` is a ctypes array of B EchoSamplerItem.  `start_pos`: one int, or a sequence /
+    tensor of B ints - every utterance samples its block at its own position (echo_sample_euler_items_pos)."""
     B, S, _ = x_init.shape
+    item_pos = item_start_positions(start_pos, B)
     p = L.EchoSamplerParams()
     p.B, p.S, p.num_steps = B, S, int(num_steps)
-    p.start_pos, p.use_latent = int(start_pos), int(use_latent)
+    p.start_pos, p.use_latent = (0 if item_pos is not None else int(start_pos or 0)), int(use_latent)
     temb_dev = temb.to(model.device).contiguous()
     p.temb = temb_dev.data_ptr()
     x0 = x_init.to(model.device, torch.float32).contiguous()
     out = torch.empty_like(x0)
+    if item_pos is not None:
+        L.check(model._lib.echo_sample_euler_items_pos(model._ctx, C.byref(p), item_structs, (C.c_int32 * B)(*item_pos), x0.data_ptr(),
+                                                       out.data_ptr(), model._stream()), model._ctx)
+        return out
     L.check(model._lib.echo_sample_euler_items(model._ctx, C.byref(p), item_structs, x0.data_ptr(), out.data_ptr(), model._stream()), model._ctx)
     return out
 

@@ -130,3 +130,12 @@ def sample_blockwise(model, speaker_latent, speaker_mask, text_input_ids, text_m
     """The README's `sample_blockwise(chunk_size=...)` (README.md:92-102) as a thin wrapper: block_sizes=[chunk_size]*k."""
     return sample_blockwise_euler_cfg_independent_guidances(model, speaker_latent, speaker_mask, text_input_ids, text_mask,
                                                             rng_seed, block_sizes=[chunk_size] * num_chunks, **sampler_kwargs)
+
+
+def stream_audio_many(model: EchoDiT, fish_ae, pca_state, requests, voices=None, max_batch: int = 24) -> Iterator[Tuple[int, torch.Tensor]]:
+    """Streaming synthesis of SEVERAL utterances that share sampler calls (`stream_batch.StreamBatcher`): `requests` is a list of dicts
+    with the keyword arguments of `StreamBatcher.open` (text_input_ids, text_mask, item_params, block_sizes, rng_seed, speaker_voice,
+    continuation_latent, x_inits).  Opens them all and yields `(request index, waveform chunk)` until every stream is done; the chunks of
+    one request, concatenated, equal `ae_decode` of its blockwise latent."""
+    from .stream_batch import stream_audio_many as _many
+    yield from _many(model, fish_ae, pca_state, requests, voices=voices, max_batch=max_batch)

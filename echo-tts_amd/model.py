@@ -135,6 +135,31 @@ class VoiceHandle:
             pass
 
 
+def item_start_positions(start_pos, batch: int) -> Optional[List[int]]:
+    """None when `start_pos` is None or one int (the reference's form); else the B per-utterance start positions as a list of ints.
+    ValueError unless there are exactly `batch` of them, all integers >= 0.  Pure host code."""
+    if start_pos is None or isinstance(start_pos, int):
+        return None
+    if isinstance(start_pos, torch.Tensor):
+        if start_pos.dim() == 0:
+            return None
+        if start_pos.dtype.is_floating_point or start_pos.dtype == torch.bool:
+            raise ValueError("start_pos: per-utterance start positions must be integers")
+        vals = start_pos.detach().to("cpu").reshape(-1).tolist()
+    else:
+        vals = list(start_pos)
+    if len(vals) != batch:
+        raise ValueError(f"start_pos: one start position per KV batch item expected ({batch}), got {len(vals)}")
+    out = []
+    for v in vals:
+        if isinstance(v, bool) or int(v) != v:
+            raise ValueError(f"start_pos: per-utterance start positions must be integers, got {v!r}")
+        if int(v) < 0:
+            raise ValueError(f"start_pos: start positions must be non-negative, got {int(v)}")
+        out.append(int(v))
+    return out
+
+
 class EchoDiT:
     """model.py:472 `EchoDiT`, inference only, executed by libechohip."""
 
@@ -337,12 +362,15 @@ class EchoDiT:
 
     # ------------------------------------------------------------------ forward (model.py:563-604)
     def forward(self, x: torch.Tensor, t: torch.Tensor, text_mask: torch.Tensor, speaker_mask: torch.Tensor,
-                kv_cache_text: KVHandle, kv_cache_speaker: KVHandle, start_pos: Optional[int] = None,
+                kv_cache_text: KVHandle, kv_cache_speaker: KVHandle, start_pos=None,
                 kv_cache_latent: Optional[KVHandle] = None) -> torch.Tensor:
+        """`start_pos`: None / an int as in the reference, or (extension) a sequence or tensor of B ints, one per KV batch item: row r is
+        then evaluated at start_pos[r % B] (streams of one batch that stand at different blocks, `echo_dit_forward_pos`)."""
         rows, S, Lz = x.shape
         B = self._kvB
         if rows % B:
             raise ValueError("batch rows must be a multiple of the KV batch")
+        item_pos = item_start_positions(start_pos, B)
         # t (rows,) - any values (model.py:563-604): the distinct timesteps get one modulation table each, row_t maps rows to them
         tt = t.detach().to("cpu").reshape(-1)
         if tt.numel() == 1:
@@ -362,6 +390,11 @@ class EchoDiT:
         son = self._row_switch(speaker_mask, kv_cache_speaker.mask, rows, kv_cache_speaker.batch, self.config.speaker_patch_size)
         xin = x.to(self._device, self._dtype).contiguous()
         out = torch.empty((rows, S, Lz), dtype=torch.float32, device=self._device)
+        if item_pos is not None:
+            L.check(self._lib.echo_dit_forward_pos(self._ctx, xin.data_ptr(), temb.data_ptr(), len(uniq), (C.c_int32 * rows)(*row_t), rows, B, S,
+                                                   (C.c_int32 * B)(*item_pos), int(kv_cache_latent is not None), (C.c_int32 * rows)(*ton),
+                                                   (C.c_int32 * rows)(*son), out.data_ptr(), self._stream()), self._ctx)
+            return out
         L.check(self._lib.echo_dit_forward_t(self._ctx, xin.data_ptr(), temb.data_ptr(), len(uniq), (C.c_int32 * rows)(*row_t), rows, B, S,
                                              int(start_pos or 0), int(kv_cache_latent is not None), (C.c_int32 * rows)(*ton),
                                              (C.c_int32 * rows)(*son), out.data_ptr(), self._stream()), self._ctx)

@@ -1,0 +1,284 @@
+"""Continuous batching for blockwise streaming: streams that arrived at different times share one sampler call per block.
+
+The reference generates an utterance block by block (inference_blockwise.py:59-121): block k is one Euler run of `block_size` latents at
+start_pos = the latents generated so far, attending to the latent-prefix KV of what exists.  `sample_blockwise_stream` does that for the
+rows of ONE request batch, which move in lockstep.  Streaming clients never arrive together, so a server with eight open streams ran eight
+batch-1 samplers.  `StreamBatcher` keeps the open streams and runs, per `step()`, one `echo_sample_euler_items_pos` call for up to
+`max_batch` of them: every row brings its own start position, request parameters and cached voice.
+
+What is rebuilt per call (stated, measured by tools/bench_stream_batch.py): the text KV of the call's rows and the latent-prefix KV of their
+stacked prefixes (one encode up to the longest prefix; the latent encoder is causal, shorter items are masked by key count and their rows
+are zero beyond their own prefix); the voices are bound from their captured caches (`EchoDiT.bind_voices`), not re-encoded.
+
+Not here: a captured text KV, batched DAC tail decode (decode stays per stream, `DACStream`), incremental prefix encoding, mixed block sizes
+or step counts inside one call (streams are grouped by them)."""
+from __future__ import annotations
+
+from dataclasses import dataclass, field
+from typing import Dict, Iterator, List, Optional, Sequence, Tuple
+
+import torch
+
+from .model import MAX_ITEMS
+
+# the per-request sampler keys of a stream: inference.ITEM_KEYS without the seed (noise is drawn per stream from `rng_seed`)
+STREAM_ITEM_KEYS = ("num_steps", "cfg_scale_text", "cfg_scale_speaker", "cfg_min_t", "cfg_max_t", "truncation_factor", "rescale_k",
+                    "rescale_sigma", "speaker_kv_scale", "speaker_kv_max_layers", "speaker_kv_min_t")
+_NO_VOICE = "\0no-voice"      # the one-masked-key voice of a stream without a speaker (inference.py:341-346), as handler.synthesize_many
+
+
+@dataclass
+class StreamState:
+    """What the planner needs to know of one open stream (pure host data), plus the device state `StreamBatcher` hangs on it."""
+    id: int
+    arrival: int                       # order of `open` calls
+    block_sizes: Tuple[int, ...]
+    num_steps: int
+    next_block: int = 0
+    waiting_since: int = 0             # the step counter's value when the stream was opened or last got a block
+    # ---- device side (unused by plan_stream_step)
+    item: Optional[dict] = None
+    ids: Optional[torch.Tensor] = None
+    tmask: Optional[torch.Tensor] = None
+    voice: object = None
+    prefix: Optional[torch.Tensor] = None      # (P, latent) fp32: continuation + every block, zero where nothing was generated yet
+    start: int = 0
+    x_inits: Optional[list] = None
+    rng: object = None
+    dec: object = None
+    extra: dict = field(default_factory=dict)
+
+    @property
+    def finished(self) -> bool:
+        return self.next_block >= len(self.block_sizes)
+
+    @property
+    def key(self) -> Optional[Tuple[int, int]]:
+        """(block_size, num_steps) of the next block: the two things one sampler call cannot mix (they set the launch geometry)."""
+        return None if self.finished else (int(self.block_sizes[self.next_block]), int(self.num_steps))
+
+
+def plan_stream_step(states: Sequence[StreamState], max_batch: int) -> List[int]:
+    """Which streams the next sampler call carries: the ids, leader first.  Pure function of the states.
+
+    The leader is the stream that has waited longest (smallest `waiting_since`, ties by arrival): a stream that was skipped - other block
+    size, other step count, or no room - is therefore first the next time.  The call is then filled, in arrival order, with up to `max_batch`
+    open streams whose next block has the leader's (block_size, num_steps).  A finished stream takes no row.  [] when nothing waits."""
+    cap = max(1, min(int(max_batch), MAX_ITEMS))
+    open_ = [s for s in states if not s.finished]
+    if not open_:
+        return []
+    leader = min(open_, key=lambda s: (s.waiting_since, s.arrival))
+    rest = sorted((s for s in open_ if s is not leader and s.key == leader.key), key=lambda s: s.arrival)
+    return [leader.id] + [s.id for s in rest[:cap - 1]]
+
+
+def schedule_ts(num_steps: int) -> torch.Tensor:
+    return torch.linspace(1.0, 0.0, int(num_steps) + 1) * 0.999          # inference.py:452,459
+
+
+def check_stream_request(item: dict, block_sizes: Sequence[int], continuation_len: int, max_pos: int) -> None:
+    """The stated limits of a stream, each a ValueError with its reason.  Host only; runs before any device work."""
+    unknown, missing = set(item) - set(STREAM_ITEM_KEYS), set(STREAM_ITEM_KEYS) - set(item)
+    if unknown or missing:
+        raise ValueError(f"stream parameters: unknown keys {sorted(unknown)}, missing keys {sorted(missing)}")
+    if not block_sizes or any(int(b) < 1 for b in block_sizes):
+        raise ValueError("block_sizes must name at least one block of at least one latent")
+    if item["speaker_kv_scale"] is not None:
+        # inference_blockwise.py:68-70 multiplies the ONE persistent speaker cache at the start of every block; inference.py:511-513 divides it
+        # again only at the step that crosses speaker_kv_min_t.  Without such a step the factor compounds block after block.  A batched call
+        # binds every voice fresh from its captured cache and scales it once: it can reproduce "scaled, then undone inside the block" only.
+        ts, mt = schedule_ts(item["num_steps"]), item["speaker_kv_min_t"]
+        undone = mt is not None and any(bool(ts[i + 1] < mt) and bool(ts[i] >= mt) for i in range(int(item["num_steps"])))
+        if not undone:
+            raise ValueError("speaker_kv_scale without a step that crosses speaker_kv_min_t: the speaker-KV scale is never undone inside a block, "
+                             "the reference then compounds the factor block after block on one persistent cache, and a cache bound fresh "
+                             "per call cannot reproduce that")
+    total = int(continuation_len) + sum(int(b) for b in block_sizes)
+    if total > max_pos:
+        raise ValueError(f"continuation_latent of {int(continuation_len)} latents plus {total - int(continuation_len)} to generate needs "
+                         f"{total} positions: longer than the RoPE table allows ({max_pos})")
+
+
+class StreamBatcher:
+    """Open streams share sampler calls.  `open()` registers a stream, `step()` runs one call for the streams `plan_stream_step` picks and
+    returns their new blocks, `step_audio()` also decodes them (one `DACStream` per stream).  Single-threaded, like the context it drives.
+
+    `voices`: a `handler.VoiceCache`, or a dict name -> (speaker_latent, speaker_mask) or 44.1 kHz audio (1, n), as
+    `handler.synthesize_many` takes it.  `open(speaker_voice=)` names one, passes a captured batch-1 `VoiceHandle`, or None (no speaker)."""
+
+    def __init__(self, model, fish_ae, pca_state, voices=None, max_batch: int = 24):
+        from .handler import VoiceCache
+        self.model, self.fish_ae, self.pca_state = model, fish_ae, pca_state
+        self.max_batch = max(1, min(int(max_batch), MAX_ITEMS))
+        self._cache = voices if isinstance(voices, VoiceCache) else VoiceCache()
+        self._registry = {} if isinstance(voices, VoiceCache) or voices is None else dict(voices)
+        self._streams: Dict[int, StreamState] = {}
+        self._next_id = 0
+        self._tick = 0
+        self.stats = {"calls": 0, "rows": 0, "ms_encode": 0.0, "ms_sample": 0.0}      # filled when `timing` is set (adds synchronisation)
+        self.timing = False
+
+    # ------------------------------------------------------------------ voices
+    def _voice(self, v):
+        from .inference import get_speaker_latent_and_mask
+        from .model import VoiceHandle
+        if isinstance(v, VoiceHandle):
+            if v.batch != 1:
+                raise ValueError("speaker_voice: a captured voice must have batch size 1")
+            return v
+        m = self.model
+        key = _NO_VOICE if v is None else v
+        if self._cache.latent(key) is None:
+            if v is None:
+                lz = m.config.latent_size
+                lat, mask = torch.zeros((1, 4, lz), device=m.device, dtype=m.dtype), torch.zeros((1, 4), device=m.device, dtype=torch.bool)
+            else:
+                src = self._registry.get(v)
+                if src is None:
+                    raise ValueError(f"speaker_voice '{v}' not found")
+                lat, mask = src if isinstance(src, (tuple, list)) else get_speaker_latent_and_mask(self.fish_ae, self.pca_state, src.to(m.device))
+            self._cache.put_latent(key, lat.to(m.device, m.dtype), mask)
+        return self._cache.speaker_kv(m, key)
+
+    # ------------------------------------------------------------------ streams
+    def open(self, text_input_ids, text_mask, item_params: dict, block_sizes: Sequence[int], rng_seed: int, speaker_voice=None,
+             continuation_latent: Optional[torch.Tensor] = None, x_inits: Optional[List[torch.Tensor]] = None) -> int:
+        """One utterance: text_input_ids / text_mask (1, Tt) or (Tt,); `item_params` = the reference's per-request sampler keys
+        (STREAM_ITEM_KEYS); `x_inits` (one (1, block, latent) or (block, latent) tensor per block) replaces the RNG draw, which is otherwise
+        the draw `sample_blockwise_stream` makes for a batch-1 request with `rng_seed`.  Returns the stream's id."""
+        m = self.model
+        item = dict(item_params)
+        cont_len = 0 if continuation_latent is None else int(continuation_latent.shape[-2])
+        check_stream_request(item, block_sizes, cont_len, int(getattr(m, "MAX_POS", 4096)))
+        if not m.has_latent_encoder:
+            raise RuntimeError("this checkpoint was loaded without the blockwise modules")
+        ids = text_input_ids.reshape(1, -1).to(m.device, torch.int32)
+        tmask = torch.ones_like(ids, dtype=torch.bool) if text_mask is None else text_mask.reshape(1, -1).to(m.device, torch.bool)
+        if x_inits is not None and len(x_inits) != len(block_sizes):
+            raise ValueError("x_inits: one noise tensor per block expected")
+        lz = m.config.latent_size
+        prefix = torch.zeros((cont_len + sum(int(b) for b in block_sizes), lz), device=m.device, dtype=torch.float32)
+        if cont_len:
+            prefix[:cont_len] = continuation_latent.reshape(cont_len, lz).to(m.device, torch.float32)
+        sid = self._next_id
+        self._next_id += 1
+        st = StreamState(id=sid, arrival=sid, block_sizes=tuple(int(b) for b in block_sizes), num_steps=int(item["num_steps"]),
+                         waiting_since=self._tick, item=item, ids=ids, tmask=tmask, voice=self._voice(speaker_voice), prefix=prefix,
+                         start=cont_len, x_inits=None if x_inits is None else list(x_inits),
+                         rng=torch.Generator(device=m.device).manual_seed(int(rng_seed)))
+        self._streams[sid] = st
+        return sid
+
+    def close(self, sid: int) -> None:
+        self._streams.pop(sid, None)
+
+    @property
+    def open_ids(self) -> List[int]:
+        return [s.id for s in self._streams.values() if not s.finished]
+
+    def latents(self, sid: int) -> torch.Tensor:
+        """(1, latents so far, latent_size) of an open stream: continuation + generated blocks."""
+        s = self._streams[sid]
+        return s.prefix[:s.start].unsqueeze(0)
+
+    def _noise(self, s: StreamState) -> torch.Tensor:
+        bs, lz = s.block_sizes[s.next_block], self.model.config.latent_size
+        if s.x_inits is not None:
+            return s.x_inits[s.next_block].reshape(1, bs, lz).to(self.model.device, torch.float32)
+        return torch.randn((1, bs, lz), device=self.model.device, dtype=torch.float32, generator=s.rng)
+
+    def step(self) -> List[Tuple[int, int, torch.Tensor]]:
+        """One sampler call.  Returns [(id, start_pos, block_latents (1, block_size, latent))] of the streams it carried ([] when none is
+        open).  A stream closes itself after its last block."""
+        out = self._step()
+        self._reap()
+        return out
+
+    @torch.inference_mode()
+    def _step(self) -> List[Tuple[int, int, torch.Tensor]]:
+        from .inference import _multiply_kv_cache_items, build_sampler_items, check_sampler_items, run_euler_items
+        picked = plan_stream_step(list(self._streams.values()), self.max_batch)
+        if not picked:
+            return []
+        m = self.model
+        rows = [self._streams[i] for i in picked]
+        B, ps = len(rows), m.config.speaker_patch_size
+        items = [dict(s.item) for s in rows]
+        check_sampler_items(items, B, B, need_seed=False)
+        arr, temb, _keep = build_sampler_items(m, items)
+        if self.timing:
+            torch.cuda.synchronize(m.device)
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+            ev[0].record()
+        # texts: padded to the call's longest, each behind its own key mask
+        Tt = max(int(s.ids.shape[1]) for s in rows)
+        ids = torch.zeros((B, Tt), device=m.device, dtype=torch.int32)
+        tmask = torch.zeros((B, Tt), device=m.device, dtype=torch.bool)
+        for b, s in enumerate(rows):
+            ids[b, :s.ids.shape[1]] = s.ids[0]
+            tmask[b, :s.tmask.shape[1]] = s.tmask[0]
+        m.get_kv_cache_text(ids, tmask)
+        kv_spk = m.bind_voices([s.voice for s in rows])
+        if any(it["speaker_kv_scale"] is not None for it in items):
+            _multiply_kv_cache_items(kv_spk, [1.0 if it["speaker_kv_scale"] is None else it["speaker_kv_scale"] for it in items],
+                                     [it["speaker_kv_max_layers"] for it in items])
+        # prefixes: one encode up to the longest item's prefix; an item's rows beyond its own prefix are zeros (finite, masked by count)
+        starts = [int(s.start) for s in rows]
+        n_lat = (max(starts) + ps - 1) // ps * ps
+        P = max(n_lat, ps)
+        stacked = torch.zeros((B, P, m.config.latent_size), device=m.device, dtype=torch.float32)
+        for b, s in enumerate(rows):
+            stacked[b, :s.start] = s.prefix[:s.start]
+        m.get_kv_cache_latent(stacked, n_latents=n_lat)
+        x0 = torch.cat([self._noise(s) for s in rows], 0)
+        if self.timing:
+            ev[1].record()
+        x = run_euler_items(m, x0, arr, rows[0].num_steps, temb, start_pos=starts, use_latent=True)
+        if self.timing:
+            ev[2].record()
+            torch.cuda.synchronize(m.device)
+            self.stats["ms_encode"] += ev[0].elapsed_time(ev[1])
+            self.stats["ms_sample"] += ev[1].elapsed_time(ev[2])
+        self.stats["calls"] += 1
+        self.stats["rows"] += B
+        self._tick += 1
+        out = []
+        for b, s in enumerate(rows):
+            bs = s.block_sizes[s.next_block]
+            s.prefix[s.start:s.start + bs] = x[b]
+            out.append((s.id, s.start, x[b:b + 1]))
+            s.start += bs
+            s.next_block += 1
+            s.waiting_since = self._tick
+        return out
+
+    def _reap(self) -> None:
+        for sid in [s.id for s in self._streams.values() if s.finished]:
+            self._streams.pop(sid)
+
+    @torch.inference_mode()
+    def step_audio(self) -> List[Tuple[int, torch.Tensor]]:
+        """`step()`, then each new block through its stream's own `DACStream` (batch 1): [(id, waveform chunk (1, 1, block_size * hop))].
+        The concatenated chunks of a stream equal `ae_decode` of its final latent."""
+        from .autoencoder import DACStream
+        out = []
+        for sid, start, block in self._step():
+            s = self._streams[sid]
+            if s.dec is None:
+                s.dec = DACStream(self.fish_ae, self.pca_state)
+                if start > 0:                    # a continuation's audio exists already: only its decoder context is needed
+                    s.dec.push(s.prefix[:start])
+            out.append((sid, s.dec.push(block[0])))
+        self._reap()
+        return out
+
+
+def stream_audio_many(model, fish_ae, pca_state, requests: Sequence[dict], voices=None, max_batch: int = 24) -> Iterator[Tuple[int, torch.Tensor]]:
+    """Generator over a list of requests (dicts with the keyword arguments of `StreamBatcher.open`): opens them all and yields
+    `(request index, waveform chunk)` block by block until every stream is done."""
+    sb = StreamBatcher(model, fish_ae, pca_state, voices=voices, max_batch=max_batch)
+    index = {sb.open(**dict(r)): i for i, r in enumerate(requests)}
+    while sb.open_ids:
+        for sid, chunk in sb.step_audio():
+            yield index[sid], chunk

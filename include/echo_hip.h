@@ -197,6 +197,28 @@ int echo_scale_speaker_kv_items(echo_ctx* ctx, const float* scales_host, const i
  * A key bias is carried only if some voice has one; the others get 0 on their keys.  Same checks as echo_voice_bind. */
 int echo_voice_bind_items(echo_ctx* ctx, const echo_voice* const* voices, int n, void* stream);
 
+/* ---- per-utterance start positions (additive: every declaration above keeps its layout and its bits; ECHO_ABI_VERSION stays 8) ----
+ * Blockwise generation (inference_blockwise.py:59-121) writes block k of an utterance at start_pos = the latents generated so far: the RoPE
+ * position of query / self key s is start_pos + s (inference_blockwise.py:91-94 -> model.py:217-232), and the block sees the first
+ * ceil(start_pos / patch) keys of the latent-prefix cache (model.py:623-636).  Streams that arrive at different times stand at different
+ * blocks; these two calls take ONE START POSITION PER UTTERANCE, so that such streams share a forward and a sampler call.
+ *   - item_start_pos: HOST table of B int32; row r of a forward uses item_start_pos[r % B].  It goes to the device once per call.
+ *   - latent keys of row r: min(cache length, ceil(item_start_pos[r % B] / patch)).
+ *   - echo_encode_latent_prefix is unchanged: encode once up to the LONGEST item's prefix.  The latent encoder is causal, so the keys an item
+ *     with a shorter prefix may see are exactly those of its own encode; the rest are masked by count.  The prefix buffer beyond an item's own
+ *     prefix must hold finite values (zeros): a masked key is multiplied by a zero probability, and 0 x NaN is not 0.
+ *   - an item at position p gets the bits a uniform call with start_pos = p gives it (same B, same caches).
+ * Fails (non-zero, echo_last_error; the context stays usable) on a NULL table, a negative position, a position + S past the rope table,
+ * 3 B > 96 rows, and on everything the call it extends fails on. */
+/* echo_dit_forward_t with a position per KV batch item (model.py:563-604; start_pos of inference_blockwise.py:91-94 per row) */
+int echo_dit_forward_pos(echo_ctx* ctx, const void* x, const void* temb, int n_t, const int32_t* row_t, int rows, int B, int S,
+                         const int32_t* item_start_pos /* host, B */, int use_latent, const int32_t* row_text_on, const int32_t* row_spk_on,
+                         float* v_out, void* stream);
+/* echo_sample_euler_items with p->start_pos ignored: item b samples its block at item_start_pos[b] (inference_blockwise.py:59-121, one
+ * loop iteration for B streams at once).  The positions' RoPE rows are gathered once, in front of the step loop. */
+int echo_sample_euler_items_pos(echo_ctx* ctx, const echo_sampler_params* p, const echo_sampler_item* items /* p->B entries */,
+                                const int32_t* item_start_pos /* host, p->B */, const float* x_init, float* latent_out, void* stream);
+
 /* inference.py:226-229 ae_decode -> autoencoder.py:1128-1132 DAC.decode_zq, one batch item:
  * latent (T, latent_size) fp32 -> wav (T * hop) fp32.
  * ECHO_BF16 context (ABI 8): the PCA inverse is evaluated in fp32 and rounded to bf16 once (inference.py:227-229), the decoder runs in bf16 and the
