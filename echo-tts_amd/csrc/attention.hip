@@ -1421,6 +1421,40 @@ __global__ void __launch_bounds__(256, 1) attn5_kernel(const AttnArgs p) {
   else attn5_body<DIAG, 2>(p);
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Per-utterance lengths (AttnArgs.qlen): the forms of attn5_kernel and attn_kernel for calls whose rows end at different
+// tokens.  Kernels of their own, so that the instantiations every other call launches keep their code.  The decision is one scalar load
+// at the top and workgroup-uniform: a block whose first query is at or beyond its row's length issues no LDS-DMA and runs no tile loop; it
+// writes zeros to its O block (nothing stale from an earlier call may reach the wo GEMM: 0 x NaN = NaN) and 0 to its `redo` word.  Every
+// other block - one that straddles the length included - runs the body of the kernel it stands for, unchanged.
+template <int NT>
+__device__ __forceinline__ void attn_zero_block(bf16_t* __restrict__ O, const long o_ld, const int nq) {
+  // thread t clears 8 bytes of column group t % 32 in query rows t / 32, t / 32 + NT / 32, ...
+  bf16_t* o = O + (long)(threadIdx.x >> 5) * o_ld + (threadIdx.x & 31) * 4;
+  for (int q = threadIdx.x >> 5; q < nq; q += NT / 32, o += (long)(NT / 32) * o_ld) *(uint2*)o = make_uint2(0u, 0u);
+}
+template <int DIAG>
+__global__ void __launch_bounds__(256, 1) attn5_qlen_kernel(const AttnArgs p) {
+  const int nq = p.q128 ? 128 : 256;
+  const int qn = __builtin_amdgcn_readfirstlane(p.qlen[blockIdx.z]);
+  if (__builtin_expect((int)blockIdx.x * nq >= qn, 0)) {
+    attn_zero_block<256>(p.O + (long)blockIdx.z * p.o_row_stride + (long)blockIdx.x * nq * p.o_ld + blockIdx.y * HD, p.o_ld, min(nq, p.S - (int)blockIdx.x * nq));
+    if (threadIdx.x == 0 && p.redo) p.redo[((long)blockIdx.z * gridDim.y + blockIdx.y) * p.redo_nb + blockIdx.x] = 0;
+    return;
+  }
+  if (p.q128 || p.S - (int)blockIdx.x * 256 <= 128) attn5_body<DIAG, 1>(p);
+  else attn5_body<DIAG, 2>(p);
+}
+__global__ void __launch_bounds__(512, 2) attn_qlen_kernel(const AttnArgs p) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int qn = __builtin_amdgcn_readfirstlane(p.qlen[blockIdx.z]);
+  if (__builtin_expect((int)blockIdx.x * QT >= qn, 0)) {
+    attn_zero_block<512>(p.O + (long)blockIdx.z * p.o_row_stride + (long)blockIdx.x * QT * p.o_ld + blockIdx.y * HD, p.o_ld, min(QT, p.S - (int)blockIdx.x * QT));
+    return;
+  }
+  attn_body<false, false, false>(p, smem, blockIdx.x, blockIdx.y, blockIdx.z, 0);
+}
+
 }  // namespace
 
 hipError_t launch_attention_bf16(const AttnArgs& a, hipStream_t st) {
@@ -1429,6 +1463,7 @@ hipError_t launch_attention_bf16(const AttnArgs& a, hipStream_t st) {
   if (a.O8 && (!(a.o8_inv > 0.0f) || (a.o8_ld & 3))) return hipErrorInvalidValue;
   for (int s = 0; s < a.nseg; ++s)
     if ((a.seg[s].vt_ld & 7) || (a.seg[s].k_ld & 7) || !a.seg[s].nkeys) return hipErrorInvalidValue;
+  if (a.qlen && (a.causal || a.O8 || a.prof)) return hipErrorInvalidValue;      // the length forms exist for the joint attention only
   static std::atomic<unsigned long long> prepared[5];
   const void* ks[5] = {(const void*)attn_kernel<false, false, false>, (const void*)attn_kernel<true, false, false>,
                        (const void*)attn_kernel<false, true, false>, (const void*)attn_kernel<true, true, false>,
@@ -1438,6 +1473,7 @@ hipError_t launch_attention_bf16(const AttnArgs& a, hipStream_t st) {
   dim3 grid((a.S + QT - 1) / QT, a.H, a.rows);
   bool bias = false;
   for (int s = 0; s < a.nseg; ++s) bias = bias || a.seg[s].bias != nullptr;
+  if (a.qlen && bias) return hipErrorInvalidValue;
   // ECHO_ATTN=4 / 5 select attn4_kernel / attn5_kernel (4 waves x 64 queries, one wave per SIMD) for the joint attention, then attn_kernel
   // for the (normally zero) workgroups whose scores left the fast kernels' range; both launches on the caller's stream.
   // Default: attn5_kernel with 256-query workgroups (two query streams per wave), or 128-query ones for grids of at most one round (below).
@@ -1466,9 +1502,13 @@ hipError_t launch_attention_bf16(const AttnArgs& a, hipStream_t st) {
       static std::atomic<unsigned long long> prep8{0};
       if (hipError_t e = ensure_dyn_lds((const void*)attn5_kernel<256>, SMEM5, prep8); e != hipSuccess) return e;
       hipLaunchKernelGGL(attn5_kernel<256>, g4, dim3(256), SMEM5, st, f);
-    } else if (variant == 4) {
+    } else if (variant == 4) {        // (with a length table too: attn4_kernel computes its padding blocks, under the per-row key counts)
       if (hipError_t e = ensure_dyn_lds((const void*)attn4_kernel<0>, SMEM4, prep4[0]); e != hipSuccess) return e;
       hipLaunchKernelGGL(attn4_kernel<0>, g4, dim3(256), SMEM4, st, f);
+    } else if (a.qlen) {              // per-utterance lengths: the same grid and block size, chosen above from the geometry alone
+      static std::atomic<unsigned long long> prepq{0};
+      if (hipError_t e = ensure_dyn_lds((const void*)attn5_qlen_kernel<0>, SMEM5, prepq); e != hipSuccess) return e;
+      hipLaunchKernelGGL(attn5_qlen_kernel<0>, g4, dim3(256), SMEM5, st, f);
     } else {
       const int di = a.prof ? (diag == 132 ? 2 : diag == 6 ? 3 : 5) : diag == 3 ? 4 : 1;
       const void* k5[6] = {nullptr, (const void*)attn5_kernel<0>, (const void*)attn5_kernel<132>, (const void*)attn5_kernel<6>, (const void*)attn5_kernel<3>,
@@ -1506,7 +1546,11 @@ hipError_t launch_attention_bf16(const AttnArgs& a, hipStream_t st) {
   }
   AttnArgs a0 = a;
   a0.q_block0 = 0; a0.redo_nb = 0; a0.redo_filter = nullptr; a0.q128 = 0;
-  if (a.prof && !a.causal && !bias) hipLaunchKernelGGL((attn_kernel<false, false, true>), grid, dim3(512), SMEM, st, a0);   // s_memtime stamps
+  if (a.qlen) {
+    static std::atomic<unsigned long long> prepq1{0};
+    if (hipError_t e = ensure_dyn_lds((const void*)attn_qlen_kernel, SMEM, prepq1); e != hipSuccess) return e;
+    hipLaunchKernelGGL(attn_qlen_kernel, grid, dim3(512), SMEM, st, a0);
+  } else if (a.prof && !a.causal && !bias) hipLaunchKernelGGL((attn_kernel<false, false, true>), grid, dim3(512), SMEM, st, a0);   // s_memtime stamps
   else if (a.causal && bias) hipLaunchKernelGGL((attn_kernel<true, true, false>), grid, dim3(512), SMEM, st, a0);
   else if (a.causal) hipLaunchKernelGGL((attn_kernel<true, false, false>), grid, dim3(512), SMEM, st, a0);
   else if (bias) hipLaunchKernelGGL((attn_kernel<false, true, false>), grid, dim3(512), SMEM, st, a0);

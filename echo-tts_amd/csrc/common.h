@@ -185,6 +185,10 @@ struct AttnArgs {
   int q128;                     // set by the launcher: attn5_kernel runs every block as 128 queries (one stream per wave), `redo` is per 128 queries  // fp8 engine with static (calibrated) activation scales: O8 != nullptr -> the epilogue writes e4m3(bf16(out) * o8_inv) bytes there
   // (same indexing as O, pitches in bytes) INSTEAD of the bf16 output: the A operand of the wo GEMM without a quantisation pass
   uint8_t* O8; long o8_ld, o8_row_stride; float o8_inv;
+  // per-utterance lengths: qlen[row] = number of leading queries of `row` that anybody reads (device, [rows]).  A workgroup
+  // whose first query is at or beyond it writes zeros to its O block and 0 to its `redo` word and does no K / V work.  nullptr (every call
+  // without a length table): the kernels above, unchanged.  Only for the joint attention (no causal mask, no per-key bias, no O8).
+  const int* qlen;
 };
 inline long attn_redo_words(int rows, int H, int S) { return (long)rows * H * ((S + 127) / 128); }      // enough for the 128-query block mode
 hipError_t launch_attention_bf16(const AttnArgs& a, hipStream_t st);
@@ -258,6 +262,22 @@ struct EulerItemsArgs {
   int init;
 };
 template <typename T> hipError_t launch_euler_items(const EulerItemsArgs& e, hipStream_t st);
+
+// Per-utterance lengths: token s of item b is padding when s >= len[b] (device table, B entries).  The length forms of the
+// sampler update and of the two staging copies never read a padding token of the caller's tensors and write zeros for it.
+struct EulerItemsLenArgs {
+  EulerItemsArgs a;
+  const int* len;           // device, B entries, 1 <= len[b] <= S
+  const float* x0;          // the caller's x_init (B, S, L): read by the init launch, valid tokens only
+};
+// init: x = x0 * init_scale for valid tokens, 0 for padding.  step: euler_items_kernel's arithmetic for valid tokens; padding keeps x = 0.
+template <typename T> hipError_t launch_euler_items_len(const EulerItemsLenArgs& e, hipStream_t st);
+// xin[(r * S + s)][l < L] = s < len[r % B] ? x[(r * S + s)][l] : 0   (x, xin of T; the columns L.. of xin stay as they are: zero)
+template <typename T> hipError_t launch_stage_x_len(const T* x, int L, T* xin, long ld_xin, int rows, int B, int S, const int* len, hipStream_t st);
+// y[(r * S + s)][l < cols] = s < len[r % B] ? float(x[(r * S + s)][l]) : 0
+template <typename T> hipError_t launch_convert_to_f32_len(const T* x, long ldx, float* y, long ldy, int rows, int B, int S, int cols, const int* len, hipStream_t st);
+// launch_rope_gather for items shorter than S: out[b * S + s] = rope[start[b] + min(s, len[b] - 1)], so that start[b] + len[b] bounds the reads
+hipError_t launch_rope_gather_len(const float2* rope, const int* start_dev, const int* len_dev, float2* out, int B, int S, hipStream_t st);
 
 // Per-item speaker-KV scaling: item b's K | V rows and its V^T rows of layers < nl[b] are multiplied by s[b] (rounding of
 // launch_scale_2d); an item with s == 1 or nl == 0 is not touched.  kv: (nB * Tn, ld) with layer l at columns [l * 2D, (l + 1) * 2D);

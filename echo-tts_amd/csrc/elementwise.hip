@@ -313,6 +313,29 @@ __global__ void euler_kernel(const EulerArgs e) {
   for (int r = 0; r < e.R_next; ++r) xin[(r * bs + tok) * e.ld_xin + l] = Num<T>::st(x);
 }
 
+// One token element of a mixed call's Euler step (CFG combine, temporal rescale, update): the ONE statement of that arithmetic, shared by
+// euler_items_kernel and its length form.
+template <typename T>
+__device__ __forceinline__ float euler_item_update(const EulerItemsArgs& e, const int item, const long tok, const int l, const long bs, float x) {
+  const EulerItem it = e.items[item];
+  const T* v = (const T*)e.v;
+  float vp = Num<T>::ld(v[tok * e.ldv + l]);
+  if (e.R == 3 && it.has_cfg) {
+    const float vut = Num<T>::ld(v[(bs + tok) * e.ldv + l]);
+    const float vus = Num<T>::ld(v[(2 * bs + tok) * e.ldv + l]);
+    const float a = __fmul_rn(it.s_text, __fsub_rn(vp, vut));
+    const float b = __fmul_rn(it.s_spk, __fsub_rn(vp, vus));
+    vp = __fadd_rn(__fadd_rn(vp, a), b);
+  }
+  if (it.rescale) {
+    float t = __fadd_rn(__fmul_rn(it.r_1mt, vp), x);
+    t = __fsub_rn(__fmul_rn(it.r_ratio, t), x);
+    vp = __fmul_rn(it.r_inv1mt, t);
+  }
+  x = __fadd_rn(x, __fmul_rn(vp, it.dt));
+  return x;
+}
+
 // The same update with per-utterance parameters (echo_sample_euler_items): item = tok / S reads its own table entry.  The arithmetic is
 // euler_kernel's, operation for operation, so an item whose entry equals a uniform call's launch scalars gets the same bits.  R == 3
 // means "some item has CFG at this step"; an item without it takes v_cond as it is (its two un-conditional rows ride along unused).
@@ -330,26 +353,59 @@ __global__ void euler_items_kernel(const EulerItemsArgs e) {
     const float s = e.init_scale[item];
     if (s != 1.0f) x = __fmul_rn(x, s);
   } else {
-    const EulerItem it = e.items[item];
-    const T* v = (const T*)e.v;
-    float vp = Num<T>::ld(v[tok * e.ldv + l]);
-    if (e.R == 3 && it.has_cfg) {
-      const float vut = Num<T>::ld(v[(bs + tok) * e.ldv + l]);
-      const float vus = Num<T>::ld(v[(2 * bs + tok) * e.ldv + l]);
-      const float a = __fmul_rn(it.s_text, __fsub_rn(vp, vut));
-      const float b = __fmul_rn(it.s_spk, __fsub_rn(vp, vus));
-      vp = __fadd_rn(__fadd_rn(vp, a), b);
-    }
-    if (it.rescale) {
-      float t = __fadd_rn(__fmul_rn(it.r_1mt, vp), x);
-      t = __fsub_rn(__fmul_rn(it.r_ratio, t), x);
-      vp = __fmul_rn(it.r_inv1mt, t);
-    }
-    x = __fadd_rn(x, __fmul_rn(vp, it.dt));
+    x = euler_item_update<T>(e, item, tok, l, bs, x);
   }
   e.x[i] = x;
   T* xin = (T*)e.xin;
   for (int r = 0; r < e.R_next; ++r) xin[(r * bs + tok) * e.ld_xin + l] = Num<T>::st(x);
+}
+
+// Per-utterance lengths.  The update of a valid token is euler_items_kernel's, operation for operation; a padding token
+// (s >= len[item]) is never read from the caller's x_init, is written as 0 by the init launch and stays 0: its update is skipped.
+template <typename T>
+__global__ void euler_items_len_kernel(const EulerItemsLenArgs p) {
+  const EulerItemsArgs& e = p.a;
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long n = (long)e.B * e.S * e.L;
+  if (i >= n) return;
+  const long tok = i / e.L;
+  const int l = (int)(i - tok * e.L);
+  const int item = (int)(tok / e.S);
+  const long bs = (long)e.B * e.S;
+  const bool valid = (int)(tok - (long)item * e.S) < p.len[item];
+  float x = 0.0f;
+  if (valid) {
+    if (e.init) {
+      x = p.x0[i];
+      const float s = e.init_scale[item];
+      if (s != 1.0f) x = __fmul_rn(x, s);
+    } else {
+      x = euler_item_update<T>(e, item, tok, l, bs, e.x[i]);
+    }
+  }
+  e.x[i] = x;
+  T* xin = (T*)e.xin;
+  for (int r = 0; r < e.R_next; ++r) xin[(r * bs + tok) * e.ld_xin + l] = Num<T>::st(x);
+}
+template <typename T>
+__global__ void stage_x_len_kernel(const T* __restrict__ x, int L, T* __restrict__ xin, long ld_xin, long n, int B, int S, const int* __restrict__ len) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const long tok = i / L;
+  const int l = (int)(i - tok * L);
+  const long r = tok / S;
+  const int s = (int)(tok - r * S);
+  xin[tok * ld_xin + l] = s < len[r % B] ? x[i] : Num<T>::st(0.0f);
+}
+template <typename T>
+__global__ void to_f32_len_kernel(const T* __restrict__ x, long ldx, float* __restrict__ y, long ldy, long n, int B, int S, int cols, const int* __restrict__ len) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const long tok = i / cols;
+  const int c = (int)(i - tok * cols);
+  const long r = tok / S;
+  const int s = (int)(tok - r * S);
+  y[tok * ldy + c] = s < len[r % B] ? Num<T>::ld(x[tok * ldx + c]) : 0.0f;
 }
 
 // 16 bytes of T
@@ -756,6 +812,26 @@ template <typename T> hipError_t launch_euler_items(const EulerItemsArgs& e, hip
   hipLaunchKernelGGL(euler_items_kernel<T>, grid1d((long)e.B * e.S * e.L), dim3(256), 0, st, e);
   return hipGetLastError();
 }
+template <typename T> hipError_t launch_euler_items_len(const EulerItemsLenArgs& p, hipStream_t st) {
+  const EulerItemsArgs& e = p.a;
+  if (!e.x || !e.xin || !p.len || (e.init ? (!e.init_scale || !p.x0) : (!e.items || !e.v)) || e.B < 1 || e.S < 1 || e.L < 1) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(euler_items_len_kernel<T>, grid1d((long)e.B * e.S * e.L), dim3(256), 0, st, p);
+  return hipGetLastError();
+}
+template <typename T>
+hipError_t launch_stage_x_len(const T* x, int L, T* xin, long ld_xin, int rows, int B, int S, const int* len, hipStream_t st) {
+  if (!x || !xin || !len || L < 1 || ld_xin < L || rows < 1 || B < 1 || S < 1) return hipErrorInvalidValue;
+  const long n = (long)rows * S * L;
+  hipLaunchKernelGGL(stage_x_len_kernel<T>, grid1d(n), dim3(256), 0, st, x, L, xin, ld_xin, n, B, S, len);
+  return hipGetLastError();
+}
+template <typename T>
+hipError_t launch_convert_to_f32_len(const T* x, long ldx, float* y, long ldy, int rows, int B, int S, int cols, const int* len, hipStream_t st) {
+  if (!x || !y || !len || cols < 1 || ldx < cols || ldy < cols || rows < 1 || B < 1 || S < 1) return hipErrorInvalidValue;
+  const long n = (long)rows * S * cols;
+  hipLaunchKernelGGL(to_f32_len_kernel<T>, grid1d(n), dim3(256), 0, st, x, ldx, y, ldy, n, B, S, cols, len);
+  return hipGetLastError();
+}
 // bandwidth kernels: enough workgroups for a few rounds of the 256 CUs, the rest of an item's vectors in the grid-stride loop
 static inline unsigned items_grid_x(long vectors) { return (unsigned)std::max(1L, std::min((vectors + 255) / 256, 2048L)); }
 template <typename T>
@@ -847,6 +923,24 @@ hipError_t launch_rope_gather(const float2* rope, const int* start_dev, float2* 
                      start_dev, (float4*)out, B, S);
   return hipGetLastError();
 }
+// rope_gather_kernel for items shorter than the call: a padding token takes the row of its item's last valid position, so
+// that the reads stay below start[b] + len[b] (what the caller has checked against the table) and every padding q / k stays finite.
+__global__ void __launch_bounds__(256) rope_gather_len_kernel(const float4* __restrict__ rope, const int* __restrict__ start, const int* __restrict__ len,
+                                                              float4* __restrict__ out, int B, int S) {
+  const long n = (long)B * S * 32;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+    const int row = (int)(i >> 5), j = (int)(i & 31);
+    const int b = row / S, s = row - b * S;
+    out[i] = rope[(long)(start[b] + min(s, len[b] - 1)) * 32 + j];
+  }
+}
+hipError_t launch_rope_gather_len(const float2* rope, const int* start_dev, const int* len_dev, float2* out, int B, int S, hipStream_t st) {
+  if (!rope || !start_dev || !len_dev || !out || B < 1 || S < 1 || ((uintptr_t)rope & 15) || ((uintptr_t)out & 15)) return hipErrorInvalidValue;
+  const long vectors = (long)B * S * 32;
+  hipLaunchKernelGGL(rope_gather_len_kernel, dim3((unsigned)std::max(1L, std::min((vectors + 255) / 256, 2048L))), dim3(256), 0, st, (const float4*)rope,
+                     start_dev, len_dev, (float4*)out, B, S);
+  return hipGetLastError();
+}
 hipError_t launch_mask_to_bias(const uint8_t* mask, float* bias, long n, hipStream_t st) {
   hipLaunchKernelGGL(mask_to_bias_kernel, grid1d(n), dim3(256), 0, st, mask, bias, n);
   return hipGetLastError();
@@ -868,6 +962,9 @@ hipError_t launch_mask_to_bias(const uint8_t* mask, float* bias, long n, hipStre
   template hipError_t launch_convert_to_f32<T>(const T*, long, float*, long, int, int, hipStream_t);                         \
   template hipError_t launch_euler<T>(const EulerArgs&, hipStream_t);                                                        \
   template hipError_t launch_euler_items<T>(const EulerItemsArgs&, hipStream_t);                                             \
+  template hipError_t launch_euler_items_len<T>(const EulerItemsLenArgs&, hipStream_t);                                      \
+  template hipError_t launch_stage_x_len<T>(const T*, int, T*, long, int, int, int, const int*, hipStream_t);                \
+  template hipError_t launch_convert_to_f32_len<T>(const T*, long, float*, long, int, int, int, int, const int*, hipStream_t); \
   template hipError_t launch_scale_kv_items<T>(T*, long, T*, long, int, int, int, const KvItemScales&, hipStream_t);         \
   template hipError_t launch_voice_gather<T>(const VoiceSrc*, int, T*, long, T*, long, int, int, int, hipStream_t);
 INST(bf16_t)

@@ -211,6 +211,11 @@ struct EngineBase {
                               int use_latent, const int32_t* ton, const int32_t* son, float* v, hipStream_t st) = 0;
   virtual int sample_euler_items_pos(const echo_sampler_params* p, const echo_sampler_item* items, const int32_t* item_pos, const float* x0,
                                      float* out, hipStream_t st) = 0;
+  // per-utterance lengths (calls that mix block sizes / sequence lengths): item_len is a host table of B entries, item_pos may be null
+  virtual int dit_forward_len(const void* x, const void* temb, int n_t, const int32_t* row_t, int rows, int B, int S, const int32_t* item_pos,
+                              const int32_t* item_len, int use_latent, const int32_t* ton, const int32_t* son, float* v, hipStream_t st) = 0;
+  virtual int sample_euler_items_len(const echo_sampler_params* p, const echo_sampler_item* items, const int32_t* item_pos, const int32_t* item_len,
+                                     const float* x0, float* out, hipStream_t st) = 0;
 };
 
 // Small host tables go to the device through a ring of pinned staging slots, without a host sync (the pattern of push_nkeys): a
@@ -299,6 +304,10 @@ struct Engine : EngineBase {
   DevBuf b_attn_keep;               // fp32 engine, per-utterance start positions: attention rows kept between the passes of attention_by_prefix_width
   DevBuf b_pos_rope;                // per-utterance start positions: [POS_TAB_BYTES of int32 start positions | B * S gathered RoPE rows]
   static constexpr size_t POS_TAB_BYTES = 512;
+  static constexpr int LEN_TAB_OFF = 64;      // per-utterance lengths: int32 entries [LEN_TAB_OFF, LEN_TAB_OFF + B) of the same table, sent in the same copy
+  const int* len_dev() const { return b_pos_rope.as<int>() + LEN_TAB_OFF; }
+  std::vector<int32_t> len_pos;     // the start positions of the running length call (a null position table resolved)
+  const int* attn_qlen = nullptr;   // set by forward_rows around the joint attention of a length call: AttnArgs.qlen
   HostStage stage_items;
   std::vector<DevBuf*> all_bufs() {
     return {&b_kv_text, &b_vt_text, &b_kv_spk, &b_vt_spk, &b_kv_lat, &b_vt_lat, &b_nkeys, &b_bias_text, &b_bias_spk,
@@ -723,6 +732,7 @@ struct Engine : EngineBase {
       if (n == 0) return fail("attention without keys");
       CK(b_attn_redo.reserve((size_t)attn_redo_words(rows, H, S) * sizeof(int)));
       a.redo = b_attn_redo.as<int>();
+      a.qlen = attn_qlen;
       if (profiling) {
         if (attn_events_used == attn_events.size()) {
           hipEvent_t e0, e1;
@@ -1236,11 +1246,13 @@ struct Engine : EngineBase {
   }
   // host_nk rows must already describe this forward (set_row_keys)
   // item_pos (host, B entries; nullptr: every item starts at start_pos): row r sees the latent-prefix keys of item r % B's own position
-  void set_row_keys(int rows, int B, int S, int start_pos, bool use_latent, const int32_t* ton, const int32_t* son, const int32_t* item_pos = nullptr) {
+  // item_len (host, B entries; nullptr: every item has S tokens): the self segment of row r ends at item r % B's own length
+  void set_row_keys(int rows, int B, int S, int start_pos, bool use_latent, const int32_t* ton, const int32_t* son, const int32_t* item_pos = nullptr,
+                    const int32_t* item_len = nullptr) {
     for (int r = 0; r < MAXROWS; ++r) {
       const int b = B > 0 ? r % B : 0;
       const bool in = r < rows;
-      host_nk[0 * MAXROWS + r] = in ? S : 0;
+      host_nk[0 * MAXROWS + r] = in ? (item_len ? item_len[b] : S) : 0;
       int nl = 0;
       const int sp = item_pos ? item_pos[b] : start_pos;
       if (in && use_latent && lat_T > 0) nl = std::min(lat_T, (sp + cfg.speaker_patch_size - 1) / cfg.speaker_patch_size);
@@ -1259,8 +1271,15 @@ struct Engine : EngineBase {
   // xin (rows*S, lat_pad) -> vout (rows*S, 128); modrow = this step's [2L][3][D] modulation table (or `segs`: per-row-range tables)
   // item_pos != nullptr: one start position per utterance; prepare_item_pos() has put the gathered RoPE rows of exactly these positions
   // into b_pos_rope (start_pos is then unused).  The RoPE consumers keep their arithmetic, base + m % modulus, on other arguments.
+  // item_len != nullptr (always with item_pos): per-utterance lengths.  The self key counts of set_row_keys are then also the bf16 attention's
+  // per-row query counts (AttnArgs.qlen): blocks of padding queries are written as zeros and cost no K / V work.
   int forward_rows(int rows, int B, int S, int start_pos, bool use_latent, const T* modrow, hipStream_t st,
-                   const std::vector<ModSeg>* segs_in = nullptr, const int32_t* item_pos = nullptr) {
+                   const std::vector<ModSeg>* segs_in = nullptr, const int32_t* item_pos = nullptr, const int32_t* item_len = nullptr) {
+    struct QlenScope {     // attention() reads attn_qlen; every exit path of this forward puts it back
+      const int*& slot;
+      QlenScope(const int*& s, const int* v) : slot(s) { slot = v; }
+      ~QlenScope() { slot = nullptr; }
+    } qlen_scope(attn_qlen, item_len && Num<T>::is_bf16 ? b_nkeys.as<int>() : nullptr);
     const std::vector<ModSeg> one = {ModSeg{0, rows, modrow}};
     const std::vector<ModSeg>& segs = segs_in ? *segs_in : one;
     const int D = cfg.model_size, L = cfg.num_layers, H = cfg.num_heads, F = cfg.intermediate_size, M = rows * S;
@@ -1469,6 +1488,53 @@ struct Engine : EngineBase {
     return ECHO_OK;
   }
 
+  // Per-utterance lengths: item b has item_len[b] tokens of the call's S, the rest of its rows is padding.  Checks both tables
+  // (item_pos == nullptr: every item at fallback_pos), sends them to the device in ONE copy through the staging ring - start positions at the
+  // head of b_pos_rope's table, lengths at LEN_TAB_OFF - and gathers the call's RoPE rows; a padding token takes the row of its item's last
+  // valid position, so start + length is what has to fit the table.  Nothing is queued when a table is refused.
+  int prepare_item_len(const int32_t* item_pos, const int32_t* item_len, int fallback_pos, int B, int S, hipStream_t st) {
+    if (!item_len) return fail("per-utterance lengths: null length table");
+    if (fp8) return fail("per-utterance lengths: not supported by the fp8 engine (dit_fp8): its e4m3 attention output has no length form; use the bf16 engine");
+    if (B < 1 || 3 * B > MAXROWS || (size_t)(LEN_TAB_OFF + B) * sizeof(int32_t) > POS_TAB_BYTES || B > LEN_TAB_OFF) return fail("per-utterance lengths: at most 32 items per call (3 B <= 96 rows)");
+    if ((text_T > 0 && text_has_bias) || (spk_T > 0 && spk_has_bias))
+      return fail("per-utterance lengths: the text / speaker cache was built from a key mask that is not a prefix (per-key bias): the length forms of the "
+                  "attention exist for prefix masks only");
+    if (S < 1) return fail("per-utterance lengths: bad sequence length");
+    if (!rope) return fail("rope table not set");
+    int32_t tab[POS_TAB_BYTES / sizeof(int32_t)] = {};
+    for (int b = 0; b < B; ++b) {
+      const int32_t sp = item_pos ? item_pos[b] : fallback_pos;
+      if (sp < 0) return fail("per-utterance lengths: a start position is negative");
+      if (item_len[b] < 1) return fail("per-utterance lengths: a length is below 1");
+      if (item_len[b] > S) return fail("per-utterance lengths: a length is above S");
+      if ((long)sp + item_len[b] > rope_npos) return fail("per-utterance lengths: a start position plus its length runs past the rope table (rope table too short)");
+      tab[b] = sp; tab[LEN_TAB_OFF + b] = item_len[b];
+    }
+    len_pos.assign(tab, tab + B);
+    CK(b_pos_rope.reserve(POS_TAB_BYTES + (size_t)B * S * 64 * sizeof(float2)));
+    CK(stage_items.push(tab, POS_TAB_BYTES, b_pos_rope.p, st));
+    CK(launch_rope_gather_len(rope, b_pos_rope.as<int>(), len_dev(), (float2*)((char*)b_pos_rope.p + POS_TAB_BYTES), B, S, st));
+    return ECHO_OK;
+  }
+  // V^T of the self segment is [rows][D][rup(S, 64)]; the QKV tails write columns < S, and the attention's last key tile reads all 64 of its
+  // columns (masked keys meet a zero probability).  Columns [S, rup(S, 64)) hold whatever a call of another geometry left there: a length call
+  // clears them once, in front of its forwards, so that nothing stale - a NaN or Inf included - is multiplied into a valid row.
+  int clear_vt_tail(int rows, int S, hipStream_t st) {
+    const int Sp = (int)rup(S, 64);
+    if (Sp == S) return ECHO_OK;
+    CK(hipMemset2DAsync(b_vt_self.as<T>() + S, (size_t)Sp * sizeof(T), 0, (size_t)(Sp - S) * sizeof(T), (size_t)rows * cfg.model_size, st));
+    return ECHO_OK;
+  }
+  int dit_forward_len(const void* x, const void* temb, int n_t, const int32_t* row_t, int rows, int B, int S, const int32_t* item_pos,
+                      const int32_t* item_len, int use_latent, const int32_t* ton, const int32_t* son, float* v, hipStream_t st) override {
+    if (!dit_ready) return fail("echo_finalize_dit was not called");
+    if (!item_len) return fail("per-utterance lengths: null length table");
+    if (B < 1 || 3 * B > MAXROWS) return fail("per-utterance lengths: at most 32 items per call (3 B <= 96 rows)");
+    if (rows < 1 || rows > MAXROWS || rows % B || B != kvB) return fail("bad rows/B");
+    CKI(prepare_item_len(item_pos, item_len, 0, B, S, st));
+    return dit_forward_any(x, temb, n_t, row_t, rows, B, S, 0, len_pos.data(), use_latent, ton, son, v, st, item_len);
+  }
+
   int dit_forward(const void* x, const void* temb, int n_t, const int32_t* row_t, int rows, int B, int S, int start_pos, int use_latent,
                   const int32_t* ton, const int32_t* son, float* v, hipStream_t st) override {
     return dit_forward_any(x, temb, n_t, row_t, rows, B, S, start_pos, nullptr, use_latent, ton, son, v, st);
@@ -1484,7 +1550,7 @@ struct Engine : EngineBase {
   }
   // temb: (n_t, E) timestep embeddings; row_t (host, rows) = which of them each row uses (nullptr: all rows use embedding 0)
   int dit_forward_any(const void* x, const void* temb, int n_t, const int32_t* row_t, int rows, int B, int S, int start_pos, const int32_t* item_pos,
-                      int use_latent, const int32_t* ton, const int32_t* son, float* v, hipStream_t st) {
+                      int use_latent, const int32_t* ton, const int32_t* son, float* v, hipStream_t st, const int32_t* item_len = nullptr) {
     if (!dit_ready) return fail("echo_finalize_dit was not called");
     if (rows < 1 || rows > MAXROWS || B < 1 || rows % B || B != kvB) return fail("bad rows/B");
     if (spk_T > 0 && (spkB < 1 || kvB % spkB)) return fail("the speaker cache's batch size must divide the text cache's");
@@ -1501,8 +1567,15 @@ struct Engine : EngineBase {
       if (!segs.empty() && segs.back().mod == mod) ++segs.back().nrows;
       else segs.push_back(ModSeg{r, 1, mod});
     }
-    set_row_keys(rows, B, S, start_pos, use_latent != 0, ton, son, item_pos);
+    set_row_keys(rows, B, S, start_pos, use_latent != 0, ton, son, item_pos, item_len);
     CKI(push_nkeys(st));
+    if (item_len) {     // the caller's padding tokens are not read: zeros take their place, and zeros leave in v
+      CK(launch_stage_x_len<T>((const T*)x, cfg.latent_size, b_xin.as<T>(), lat_pad, rows, B, S, len_dev(), st));
+      CKI(clear_vt_tail(rows, S, st));
+      CKI(forward_rows(rows, B, S, start_pos, use_latent != 0, b_mod.as<T>(), st, &segs, item_pos, item_len));
+      CK(launch_convert_to_f32_len<T>(b_vout.as<T>(), 128, v, cfg.latent_size, rows, B, S, cfg.latent_size, len_dev(), st));
+      return ECHO_OK;
+    }
     // x (M, latent) -> xin (M, lat_pad) zero padded
     CK(hipMemcpy2DAsync(b_xin.p, lat_pad * sizeof(T), x, cfg.latent_size * sizeof(T), cfg.latent_size * sizeof(T), M,
                         hipMemcpyDeviceToDevice, st));
@@ -1578,9 +1651,17 @@ struct Engine : EngineBase {
     if (p && (p->B < 1 || 3 * p->B > MAXROWS)) return fail("per-utterance start positions: at most 32 items per call (3 B <= 96 rows)");
     return sample_euler_items_any(p, items, item_pos, true, x0, out, st);
   }
+  int sample_euler_items_len(const echo_sampler_params* p, const echo_sampler_item* items, const int32_t* item_pos, const int32_t* item_len,
+                             const float* x0, float* out, hipStream_t st) override {
+    if (!item_len) return fail("per-utterance lengths: null length table");
+    if (p && (p->B < 1 || 3 * p->B > MAXROWS)) return fail("per-utterance lengths: at most 32 items per call (3 B <= 96 rows)");
+    return sample_euler_items_any(p, items, item_pos, true, x0, out, st, item_len);
+  }
   // with_pos: p->start_pos is ignored, item b starts at item_pos[b] (host, B entries)
+  // item_len (host, B entries, with_pos): per-utterance lengths; item_pos may then be null (p->start_pos for every item).  The length forms of
+  // the staging and update kernels run instead of the memcpy and euler_items_kernel: x_t of a padding token is 0 from the first launch on.
   int sample_euler_items_any(const echo_sampler_params* p, const echo_sampler_item* items, const int32_t* item_pos, bool with_pos, const float* x0,
-                             float* out, hipStream_t st) {
+                             float* out, hipStream_t st, const int32_t* item_len = nullptr) {
     if (!dit_ready) return fail("echo_finalize_dit was not called");
     if (!p || !items) return fail("mixed sampler call: null params / items");
     const int B = p->B, S = p->S, N = p->num_steps, Lz = cfg.latent_size;
@@ -1620,6 +1701,10 @@ struct Engine : EngineBase {
       memset(&unscale[i], 0, sizeof(KvItemScales));
       if (has_unscale[i]) CKI(kv_slot_scales(us.data(), ul.data(), B, unscale[i]));
     }
+    if (item_len) {
+      CKI(prepare_item_len(item_pos, item_len, p->start_pos, B, S, st));
+      item_pos = len_pos.data();
+    } else
     if (with_pos) CKI(prepare_item_pos(item_pos, B, S, st));      // refuses a null table / a position past the rope table before any work is queued
     const int rows3 = 3 * B;
     CKI(reserve_dit_ws(rows3 * S, rows3, S));
@@ -1639,12 +1724,13 @@ struct Engine : EngineBase {
       CK(stage_items.push(blob.data(), blob.size(), b_items.p, st));
     }
     const EulerItem* tab_dev = b_items.as<EulerItem>();
-    CK(hipMemcpyAsync(xs, x0, (size_t)B * S * Lz * sizeof(float), hipMemcpyDeviceToDevice, st));
+    if (!item_len) CK(hipMemcpyAsync(xs, x0, (size_t)B * S * Lz * sizeof(float), hipMemcpyDeviceToDevice, st));
+    else CKI(clear_vt_tail(rows3, S, st));
     CKI(compute_mod((const T*)p->temb, N, st));
     if (profiling) CK(hipEventRecord(ev[1], st));
     std::vector<int32_t> ton(rows3, 1), son(rows3, 1);
     for (int b = 0; b < B; ++b) { ton[B + b] = 0; son[2 * B + b] = 0; }
-    set_row_keys(rows3, B, S, p->start_pos, p->use_latent != 0, ton.data(), son.data(), with_pos ? item_pos : nullptr);
+    set_row_keys(rows3, B, S, p->start_pos, p->use_latent != 0, ton.data(), son.data(), with_pos ? item_pos : nullptr, item_len);
     CKI(push_nkeys(st));
     const long modstride = (long)2 * cfg.num_layers * 3 * cfg.model_size;
     EulerItemsArgs e;
@@ -1653,16 +1739,22 @@ struct Engine : EngineBase {
     e.B = B; e.S = S; e.L = Lz; e.R = 1;
     e.R_next = any_cfg[0] ? 3 : 1;
     e.init = 1; e.init_scale = (const float*)((const char*)b_items.p + tab_bytes); e.items = tab_dev;
-    CK(launch_euler_items<T>(e, st));
+    auto update = [&]() -> hipError_t {
+      if (!item_len) return launch_euler_items<T>(e, st);
+      EulerItemsLenArgs el;
+      el.a = e; el.len = len_dev(); el.x0 = x0;
+      return launch_euler_items_len<T>(el, st);
+    };
+    CK(update());
     for (int i = 0; i < N; ++i) {
       const int rows = any_cfg[i] ? rows3 : B;
-      CKI(forward_rows(rows, B, S, p->start_pos, p->use_latent != 0, b_mod.as<T>() + (long)i * modstride, st, nullptr, with_pos ? item_pos : nullptr));
+      CKI(forward_rows(rows, B, S, p->start_pos, p->use_latent != 0, b_mod.as<T>() + (long)i * modstride, st, nullptr, with_pos ? item_pos : nullptr, item_len));
       if (has_unscale[i]) CKI(launch_kv_slot_scales(unscale[i], st));
       e.init = 0;
       e.R = any_cfg[i] ? 3 : 1;
       e.R_next = (i + 1 < N && any_cfg[i + 1]) ? 3 : 1;
       e.items = tab_dev + (size_t)i * B;
-      CK(launch_euler_items<T>(e, st));
+      CK(update());
     }
     CK(hipMemcpyAsync(out, xs, (size_t)B * S * Lz * sizeof(float), hipMemcpyDeviceToDevice, st));
     if (profiling) {
@@ -2561,6 +2653,15 @@ int echo_dit_forward_pos(echo_ctx* ctx, const void* x, const void* temb, int n_t
 int echo_sample_euler_items_pos(echo_ctx* ctx, const echo_sampler_params* p, const echo_sampler_item* items, const int32_t* item_start_pos,
                                 const float* x_init, float* latent_out, void* stream) {
   return ctx ? ctx->eng->sample_euler_items_pos(p, items, item_start_pos, x_init, latent_out, (hipStream_t)stream) : ECHO_ERR;
+}
+int echo_dit_forward_len(echo_ctx* ctx, const void* x, const void* temb, int n_t, const int32_t* row_t, int rows, int B, int S,
+                         const int32_t* item_start_pos, const int32_t* item_len, int use_latent, const int32_t* ton, const int32_t* son, float* v_out,
+                         void* stream) {
+  return ctx ? ctx->eng->dit_forward_len(x, temb, n_t, row_t, rows, B, S, item_start_pos, item_len, use_latent, ton, son, v_out, (hipStream_t)stream) : ECHO_ERR;
+}
+int echo_sample_euler_items_len(echo_ctx* ctx, const echo_sampler_params* p, const echo_sampler_item* items, const int32_t* item_start_pos,
+                                const int32_t* item_len, const float* x_init, float* latent_out, void* stream) {
+  return ctx ? ctx->eng->sample_euler_items_len(p, items, item_start_pos, item_len, x_init, latent_out, (hipStream_t)stream) : ECHO_ERR;
 }
 int echo_scale_speaker_kv_items(echo_ctx* ctx, const float* scales_host, const int32_t* max_layers_host, int n, void* stream) {
   return ctx ? ctx->eng->scale_speaker_kv_items(scales_host, max_layers_host, n, (hipStream_t)stream) : ECHO_ERR;

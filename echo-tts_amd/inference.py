@@ -11,6 +11,7 @@ known-answer tests generated from the reference (tests/golden/meta.json).
 from __future__ import annotations
 
 import ctypes as C
+import numbers
 import re
 from dataclasses import dataclass
 from typing import Callable, List, Optional, Sequence, Tuple
@@ -19,7 +20,7 @@ import torch
 
 from . import _lib as L
 from .autoencoder import DAC
-from .model import MAX_ITEMS, EchoDiT, KVHandle, item_start_positions, timestep_embedding
+from .model import MAX_ITEMS, EchoDiT, KVHandle, item_lengths, item_start_positions, timestep_embedding
 
 # --------------------------------------------------------------------------- text front end
 _REPLACEMENTS = (("…", "..."), ("’", "'"), ("”", '"'), ("\n", " "), (":", ","), (";", ","), ("—", ", "))
@@ -349,11 +350,14 @@ def check_sampler_items(items, batch: int, voice_slots: int, need_seed: bool = T
 
 
 def run_euler_items(model: EchoDiT, x_init: torch.Tensor, item_structs, num_steps: int, temb: torch.Tensor, start_pos=0,
-                    use_latent: bool = False) -> torch.Tensor:
+                    use_latent: bool = False, lengths=None) -> torch.Tensor:
     """One echo_sample_euler_items call: `item_structs` is a ctypes array of B EchoSamplerItem.  `start_pos`: one int, or a sequence /
-    tensor of B ints - every utterance samples its block at its own position (echo_sample_euler_items_pos)."""
+    tensor of B ints - every utterance samples its block at its own position (echo_sample_euler_items_pos).  `lengths`: a sequence / tensor
+    of B ints, 1 <= n <= S - item b samples lengths[b] latents; `x_init` beyond them is never read and the result is exactly 0 there
+    (echo_sample_euler_items_len)."""
     B, S, _ = x_init.shape
     item_pos = item_start_positions(start_pos, B)
+    item_len = item_lengths(lengths, B, S, item_pos if item_pos is not None else start_pos, model.MAX_POS)
     p = L.EchoSamplerParams()
     p.B, p.S, p.num_steps = B, S, int(num_steps)
     p.start_pos, p.use_latent = (0 if item_pos is not None else int(start_pos or 0)), int(use_latent)
@@ -361,6 +365,11 @@ def run_euler_items(model: EchoDiT, x_init: torch.Tensor, item_structs, num_step
     p.temb = temb_dev.data_ptr()
     x0 = x_init.to(model.device, torch.float32).contiguous()
     out = torch.empty_like(x0)
+    if item_len is not None:
+        pos = (C.c_int32 * B)(*item_pos) if item_pos is not None else None       # NULL: p.start_pos for every item
+        L.check(model._lib.echo_sample_euler_items_len(model._ctx, C.byref(p), item_structs, pos, (C.c_int32 * B)(*item_len), x0.data_ptr(),
+                                                       out.data_ptr(), model._stream()), model._ctx)
+        return out
     if item_pos is not None:
         L.check(model._lib.echo_sample_euler_items_pos(model._ctx, C.byref(p), item_structs, (C.c_int32 * B)(*item_pos), x0.data_ptr(),
                                                        out.data_ptr(), model._stream()), model._ctx)
@@ -403,17 +412,25 @@ def _multiply_kv_cache_items(cache: KVHandle, scales, max_layers) -> None:
 
 @torch.inference_mode()
 def sample_euler_items(model: EchoDiT, speaker_latent, speaker_mask, text_input_ids: torch.Tensor, text_mask: torch.Tensor, items, *,
-                       sequence_length: int | None = None, x_init: torch.Tensor | None = None, speaker_kv=None) -> torch.Tensor:
+                       sequence_length=None, x_init: torch.Tensor | None = None, speaker_kv=None):
     """reference inference.py:427-517 for B utterances that each bring their OWN request parameters: `items` is a list of B dicts
     with exactly the reference's per-request keys (ITEM_KEYS); row b of the result is what `sample_euler_cfg_independent_guidances`
-    computes for row b with items[b].  Per call, not per item: `num_steps` (all items must agree: ValueError) and
-    `sequence_length`.  At most 32 items.  `speaker_kv`: one VoiceHandle shared by all rows, or a list of B batch-1 VoiceHandles
+    computes for row b with items[b].  Per call, not per item: `num_steps` (all items must agree: ValueError).  `sequence_length`: an int
+    (every item, the result is a (B, S, latent) tensor), or a list of one length per item: item b's noise is then the (1, len[b], latent)
+    draw it would get alone, the call runs at the longest length with the others padded (`run_euler_items(lengths=)`), and the result is a
+    list of (len[b], latent) tensors.  At most 32 items.  `speaker_kv`: one VoiceHandle shared by all rows, or a list of B batch-1 VoiceHandles
     (one cached voice per row, `EchoDiT.bind_voices`); otherwise `speaker_latent` (B or 1 rows) is encoded.  Item b's noise is a
     (1, S, latent) draw from items[b]["rng_seed"] - the noise the request would get alone - unless `x_init` is given."""
     if sequence_length is None:
         sequence_length = 640
     items = [dict(it) for it in items]
     B = int(text_input_ids.shape[0])
+    lengths = None
+    if isinstance(sequence_length, numbers.Integral):
+        sequence_length = int(sequence_length)
+    else:
+        lengths = item_lengths(sequence_length, B, max(int(v) for v in sequence_length) if len(sequence_length) else 1)
+        sequence_length = max(lengths)
     per_row_voices = isinstance(speaker_kv, (list, tuple))
     if per_row_voices:
         if len(speaker_kv) != B:
@@ -434,10 +451,18 @@ def sample_euler_items(model: EchoDiT, speaker_latent, speaker_mask, text_input_
     if any(it["speaker_kv_scale"] is not None for it in items):
         _multiply_kv_cache_items(kv_spk, [1.0 if it["speaker_kv_scale"] is None else it["speaker_kv_scale"] for it in items],
                                  [it["speaker_kv_max_layers"] for it in items])
-    if x_init is None:
-        lz = model.config.latent_size
+    lz = model.config.latent_size
+    if x_init is None and lengths is not None:
+        x_init = torch.zeros((B, sequence_length, lz), device=device, dtype=torch.float32)
+        for b, it in enumerate(items):
+            x_init[b, :lengths[b]] = torch.randn((1, lengths[b], lz), device=device, dtype=torch.float32,
+                                                 generator=torch.Generator(device=device).manual_seed(int(it["rng_seed"])))[0]
+    elif x_init is None:
         x_init = torch.cat([torch.randn((1, sequence_length, lz), device=device, dtype=torch.float32,
                                         generator=torch.Generator(device=device).manual_seed(int(it["rng_seed"]))) for it in items], 0)
+    if lengths is not None:
+        out = run_euler_items(model, x_init, arr, int(items[0]["num_steps"]), temb, lengths=lengths)
+        return [out[b, :lengths[b]] for b in range(B)]
     return run_euler_items(model, x_init, arr, int(items[0]["num_steps"]), temb)
 
 

@@ -160,6 +160,45 @@ def item_start_positions(start_pos, batch: int) -> Optional[List[int]]:
     return out
 
 
+class LengthTableError(L.EchoHipError, ValueError):
+    """A per-utterance length the engine would refuse (below 1, above S, start + length beyond the RoPE table), found on the host."""
+
+
+def item_lengths(lengths, batch: int, S: int, start_positions=None, max_pos: Optional[int] = None) -> Optional[List[int]]:
+    """None when `lengths` is None; else the B per-utterance lengths as a list of ints (mirrors `item_start_positions`).  ValueError unless
+    there are exactly `batch` of them, all integers; LengthTableError (an EchoHipError and a ValueError) unless 1 <= n <= S and, with `max_pos`
+    given, start + n <= max_pos for item b's start position (`start_positions`: None = 0, an int, or a list of B).  Pure host code."""
+    if lengths is None:
+        return None
+    if isinstance(lengths, torch.Tensor):
+        if lengths.dtype.is_floating_point or lengths.dtype == torch.bool:
+            raise ValueError("lengths: per-utterance lengths must be integers")
+        vals = lengths.detach().to("cpu").reshape(-1).tolist()
+    elif isinstance(lengths, int):
+        raise ValueError(f"lengths: one length per KV batch item expected ({batch}), got a single int")
+    else:
+        vals = list(lengths)
+    if len(vals) != batch:
+        raise ValueError(f"lengths: one length per KV batch item expected ({batch}), got {len(vals)}")
+    out = []
+    for v in vals:
+        if isinstance(v, bool) or int(v) != v:
+            raise ValueError(f"lengths: per-utterance lengths must be integers, got {v!r}")
+        out.append(int(v))
+    if start_positions is None or isinstance(start_positions, int):
+        starts = [int(start_positions or 0)] * batch
+    else:
+        starts = [int(p) for p in start_positions]
+    for b, n in enumerate(out):
+        if n < 1:
+            raise LengthTableError(f"lengths: a length is below 1 (item {b}: {n})")
+        if n > S:
+            raise LengthTableError(f"lengths: a length is above S (item {b}: {n} > {S})")
+        if max_pos is not None and starts[b] + n > max_pos:
+            raise LengthTableError(f"lengths: a start position plus its length runs past the rope table (item {b}: {starts[b]} + {n} > {max_pos})")
+    return out
+
+
 class EchoDiT:
     """model.py:472 `EchoDiT`, inference only, executed by libechohip."""
 
@@ -363,14 +402,17 @@ class EchoDiT:
     # ------------------------------------------------------------------ forward (model.py:563-604)
     def forward(self, x: torch.Tensor, t: torch.Tensor, text_mask: torch.Tensor, speaker_mask: torch.Tensor,
                 kv_cache_text: KVHandle, kv_cache_speaker: KVHandle, start_pos=None,
-                kv_cache_latent: Optional[KVHandle] = None) -> torch.Tensor:
+                kv_cache_latent: Optional[KVHandle] = None, lengths=None) -> torch.Tensor:
         """`start_pos`: None / an int as in the reference, or (extension) a sequence or tensor of B ints, one per KV batch item: row r is
-        then evaluated at start_pos[r % B] (streams of one batch that stand at different blocks, `echo_dit_forward_pos`)."""
+        then evaluated at start_pos[r % B] (streams of one batch that stand at different blocks, `echo_dit_forward_pos`).
+        `lengths` (extension): a sequence or tensor of B ints, 1 <= n <= S: item b owns the first lengths[b] tokens of its rows, the rest is
+        padding that is never read and comes back as zeros (`echo_dit_forward_len`).  Not with `fp8=True` (EchoHipError)."""
         rows, S, Lz = x.shape
         B = self._kvB
         if rows % B:
             raise ValueError("batch rows must be a multiple of the KV batch")
         item_pos = item_start_positions(start_pos, B)
+        item_len = item_lengths(lengths, B, S, item_pos if item_pos is not None else start_pos, self.MAX_POS)
         # t (rows,) - any values (model.py:563-604): the distinct timesteps get one modulation table each, row_t maps rows to them
         tt = t.detach().to("cpu").reshape(-1)
         if tt.numel() == 1:
@@ -390,6 +432,12 @@ class EchoDiT:
         son = self._row_switch(speaker_mask, kv_cache_speaker.mask, rows, kv_cache_speaker.batch, self.config.speaker_patch_size)
         xin = x.to(self._device, self._dtype).contiguous()
         out = torch.empty((rows, S, Lz), dtype=torch.float32, device=self._device)
+        if item_len is not None:
+            pos = item_pos if item_pos is not None else [int(start_pos or 0)] * B
+            L.check(self._lib.echo_dit_forward_len(self._ctx, xin.data_ptr(), temb.data_ptr(), len(uniq), (C.c_int32 * rows)(*row_t), rows, B, S,
+                                                   (C.c_int32 * B)(*pos), (C.c_int32 * B)(*item_len), int(kv_cache_latent is not None),
+                                                   (C.c_int32 * rows)(*ton), (C.c_int32 * rows)(*son), out.data_ptr(), self._stream()), self._ctx)
+            return out
         if item_pos is not None:
             L.check(self._lib.echo_dit_forward_pos(self._ctx, xin.data_ptr(), temb.data_ptr(), len(uniq), (C.c_int32 * rows)(*row_t), rows, B, S,
                                                    (C.c_int32 * B)(*item_pos), int(kv_cache_latent is not None), (C.c_int32 * rows)(*ton),

@@ -10,8 +10,12 @@ What is rebuilt per call (stated, measured by tools/bench_stream_batch.py): the 
 stacked prefixes (one encode up to the longest prefix; the latent encoder is causal, shorter items are masked by key count and their rows
 are zero beyond their own prefix); the voices are bound from their captured caches (`EchoDiT.bind_voices`), not re-encoded.
 
-Not here: a captured text KV, batched DAC tail decode (decode stays per stream, `DACStream`), incremental prefix encoding, mixed block sizes
-or step counts inside one call (streams are grouped by them)."""
+Mixed block sizes (`StreamBatcher(mix_block_sizes=True)`, `plan_stream_step_mixed`): a call is then keyed by `num_steps` alone and runs at
+the largest block size among its streams; a shorter block rides along as a padded row with its own length (`echo_sample_euler_items_len`).
+`max_pad_fraction` bounds the share of padded tokens a call may carry.
+
+Not here: a captured text KV, batched DAC tail decode (decode stays per stream, `DACStream`), incremental prefix encoding, mixed step
+counts inside one call (streams are grouped by them)."""
 from __future__ import annotations
 
 from dataclasses import dataclass, field
@@ -73,6 +77,34 @@ def plan_stream_step(states: Sequence[StreamState], max_batch: int) -> List[int]
     return [leader.id] + [s.id for s in rest[:cap - 1]]
 
 
+def padded_share(block_sizes: Sequence[int]) -> float:
+    """sum(S_call - b_i) / (n * S_call) of one call, S_call = the largest block size in it: the share of its token rows that is padding."""
+    n, s_call = len(block_sizes), max(int(b) for b in block_sizes)
+    return sum(s_call - int(b) for b in block_sizes) / float(n * s_call)
+
+
+def plan_stream_step_mixed(states: Sequence[StreamState], max_batch: int, max_pad_fraction: Optional[float] = None) -> List[int]:
+    """`plan_stream_step` for calls that mix block sizes: the key of a call is `num_steps` alone.  Pure function of the states.
+
+    The leader is chosen as there (longest wait, ties by arrival).  The call is filled in arrival order with open streams of the leader's
+    `num_steps`; a candidate is skipped when taking it would raise the call's padded share (`padded_share` of the block sizes taken so far
+    plus its own) above `max_pad_fraction` (None: no limit).  A skipped stream keeps its `waiting_since` and so leads sooner the next time."""
+    cap = max(1, min(int(max_batch), MAX_ITEMS))
+    open_ = [s for s in states if not s.finished]
+    if not open_:
+        return []
+    leader = min(open_, key=lambda s: (s.waiting_since, s.arrival))
+    picked, sizes = [leader.id], [leader.key[0]]
+    for s in sorted((s for s in open_ if s is not leader and int(s.num_steps) == int(leader.num_steps)), key=lambda s: s.arrival):
+        if len(picked) >= cap:
+            break
+        if max_pad_fraction is not None and padded_share(sizes + [s.key[0]]) > float(max_pad_fraction):
+            continue
+        picked.append(s.id)
+        sizes.append(s.key[0])
+    return picked
+
+
 def schedule_ts(num_steps: int) -> torch.Tensor:
     return torch.linspace(1.0, 0.0, int(num_steps) + 1) * 0.999          # inference.py:452,459
 
@@ -105,18 +137,24 @@ class StreamBatcher:
     returns their new blocks, `step_audio()` also decodes them (one `DACStream` per stream).  Single-threaded, like the context it drives.
 
     `voices`: a `handler.VoiceCache`, or a dict name -> (speaker_latent, speaker_mask) or 44.1 kHz audio (1, n), as
-    `handler.synthesize_many` takes it.  `open(speaker_voice=)` names one, passes a captured batch-1 `VoiceHandle`, or None (no speaker)."""
+    `handler.synthesize_many` takes it.  `open(speaker_voice=)` names one, passes a captured batch-1 `VoiceHandle`, or None (no speaker).
 
-    def __init__(self, model, fish_ae, pca_state, voices=None, max_batch: int = 24):
+    `mix_block_sizes=True`: streams whose next blocks differ in size share a call (`plan_stream_step_mixed`, bounded by `max_pad_fraction`);
+    the default keeps one call per (block_size, num_steps)."""
+
+    def __init__(self, model, fish_ae, pca_state, voices=None, max_batch: int = 24, mix_block_sizes: bool = False,
+                 max_pad_fraction: Optional[float] = None):
         from .handler import VoiceCache
         self.model, self.fish_ae, self.pca_state = model, fish_ae, pca_state
         self.max_batch = max(1, min(int(max_batch), MAX_ITEMS))
+        self.mix_block_sizes, self.max_pad_fraction = bool(mix_block_sizes), max_pad_fraction
         self._cache = voices if isinstance(voices, VoiceCache) else VoiceCache()
         self._registry = {} if isinstance(voices, VoiceCache) or voices is None else dict(voices)
         self._streams: Dict[int, StreamState] = {}
         self._next_id = 0
         self._tick = 0
-        self.stats = {"calls": 0, "rows": 0, "ms_encode": 0.0, "ms_sample": 0.0}      # filled when `timing` is set (adds synchronisation)
+        # ms_*: filled when `timing` is set (adds synchronisation); tokens / pad_tokens: token rows the calls carried / of them padding
+        self.stats = {"calls": 0, "rows": 0, "ms_encode": 0.0, "ms_sample": 0.0, "tokens": 0, "pad_tokens": 0}
         self.timing = False
 
     # ------------------------------------------------------------------ voices
@@ -198,7 +236,10 @@ class StreamBatcher:
     @torch.inference_mode()
     def _step(self) -> List[Tuple[int, int, torch.Tensor]]:
         from .inference import _multiply_kv_cache_items, build_sampler_items, check_sampler_items, run_euler_items
-        picked = plan_stream_step(list(self._streams.values()), self.max_batch)
+        if self.mix_block_sizes:
+            picked = plan_stream_step_mixed(list(self._streams.values()), self.max_batch, self.max_pad_fraction)
+        else:
+            picked = plan_stream_step(list(self._streams.values()), self.max_batch)
         if not picked:
             return []
         m = self.model
@@ -231,10 +272,20 @@ class StreamBatcher:
         for b, s in enumerate(rows):
             stacked[b, :s.start] = s.prefix[:s.start]
         m.get_kv_cache_latent(stacked, n_latents=n_lat)
-        x0 = torch.cat([self._noise(s) for s in rows], 0)
+        sizes = [int(s.block_sizes[s.next_block]) for s in rows]
+        mixed = len(set(sizes)) > 1                  # only with mix_block_sizes: every stream's own noise in a zero (B, S_call, latent) tensor
+        if mixed:
+            x0 = torch.zeros((B, max(sizes), m.config.latent_size), device=m.device, dtype=torch.float32)
+            for b, s in enumerate(rows):
+                x0[b, :sizes[b]] = self._noise(s)[0]
+        else:
+            x0 = torch.cat([self._noise(s) for s in rows], 0)
         if self.timing:
             ev[1].record()
-        x = run_euler_items(m, x0, arr, rows[0].num_steps, temb, start_pos=starts, use_latent=True)
+        if mixed:
+            x = run_euler_items(m, x0, arr, rows[0].num_steps, temb, start_pos=starts, use_latent=True, lengths=sizes)
+        else:
+            x = run_euler_items(m, x0, arr, rows[0].num_steps, temb, start_pos=starts, use_latent=True)
         if self.timing:
             ev[2].record()
             torch.cuda.synchronize(m.device)
@@ -242,12 +293,14 @@ class StreamBatcher:
             self.stats["ms_sample"] += ev[1].elapsed_time(ev[2])
         self.stats["calls"] += 1
         self.stats["rows"] += B
+        self.stats["tokens"] += B * max(sizes)
+        self.stats["pad_tokens"] += B * max(sizes) - sum(sizes)
         self._tick += 1
         out = []
         for b, s in enumerate(rows):
             bs = s.block_sizes[s.next_block]
-            s.prefix[s.start:s.start + bs] = x[b]
-            out.append((s.id, s.start, x[b:b + 1]))
+            s.prefix[s.start:s.start + bs] = x[b, :bs]
+            out.append((s.id, s.start, x[b:b + 1, :bs]))
             s.start += bs
             s.next_block += 1
             s.waiting_since = self._tick
@@ -274,10 +327,12 @@ class StreamBatcher:
         return out
 
 
-def stream_audio_many(model, fish_ae, pca_state, requests: Sequence[dict], voices=None, max_batch: int = 24) -> Iterator[Tuple[int, torch.Tensor]]:
+def stream_audio_many(model, fish_ae, pca_state, requests: Sequence[dict], voices=None, max_batch: int = 24, mix_block_sizes: bool = False,
+                      max_pad_fraction: Optional[float] = None) -> Iterator[Tuple[int, torch.Tensor]]:
     """Generator over a list of requests (dicts with the keyword arguments of `StreamBatcher.open`): opens them all and yields
-    `(request index, waveform chunk)` block by block until every stream is done."""
-    sb = StreamBatcher(model, fish_ae, pca_state, voices=voices, max_batch=max_batch)
+    `(request index, waveform chunk)` block by block until every stream is done.  `mix_block_sizes` / `max_pad_fraction`: `StreamBatcher`."""
+    sb = StreamBatcher(model, fish_ae, pca_state, voices=voices, max_batch=max_batch, mix_block_sizes=mix_block_sizes,
+                       max_pad_fraction=max_pad_fraction)
     index = {sb.open(**dict(r)): i for i, r in enumerate(requests)}
     while sb.open_ids:
         for sid, chunk in sb.step_audio():

@@ -219,6 +219,29 @@ int echo_dit_forward_pos(echo_ctx* ctx, const void* x, const void* temb, int n_t
 int echo_sample_euler_items_pos(echo_ctx* ctx, const echo_sampler_params* p, const echo_sampler_item* items /* p->B entries */,
                                 const int32_t* item_start_pos /* host, p->B */, const float* x_init, float* latent_out, void* stream);
 
+/* ---- per-utterance lengths (additive: every declaration above keeps its layout and its bits; ECHO_ABI_VERSION stays 8) ----
+ * One forward / one sampler call for utterances of DIFFERENT lengths (streams that stand at blocks of different sizes, sentences that
+ * need different sequence lengths).  The tensors stay rectangular: (rows or B, S, latent); item b owns the first item_len[b] tokens of
+ * its rows, 1 <= item_len[b] <= S, the rest is padding.
+ *   - self keys of row r: item_len[r % B].  Position, latent-prefix, text and speaker keys as in the position calls.
+ *   - valid output rows of an item depend on nothing at a padding position: not on the caller's x / x_init there (never read; NaN and Inf
+ *     included), not on what an earlier call left in the workspace, not on the other items' lengths or contents.
+ *   - padding rows of v_out / latent_out are written as zeros; in the sampler x_t stays exactly 0 there through every step.
+ *   - all lengths equal to S: the bits of echo_dit_forward_pos / echo_sample_euler_items_pos.
+ *   - NOT claimed: that an item of length n inside a longer call has the bits of a uniform call with S = n (other M, other GEMM plans).
+ *   - padding is still computed by the GEMMs (cost: S - item_len[b] token rows per item row); the bf16 attention skips blocks of padding queries.
+ *   - item_start_pos may be NULL: every item at 0 (forward) / at p->start_pos (sampler).  Both tables go to the device in one copy.
+ * Fails (non-zero, echo_last_error; nothing is queued, the context stays usable) on a NULL length table, a length below 1 or above S, a start
+ * position plus length past the rope table, 3 B > 96 rows, a context created with dit_fp8 (the e4m3 attention output has no length form),
+ * a text or speaker cache built from a key mask that is not a prefix (its per-key bias takes the biased attention kernel, which has no length form),
+ * and on everything the position calls fail on. */
+int echo_dit_forward_len(echo_ctx* ctx, const void* x, const void* temb, int n_t, const int32_t* row_t, int rows, int B, int S,
+                         const int32_t* item_start_pos /* host, B, may be NULL */, const int32_t* item_len /* host, B */, int use_latent,
+                         const int32_t* row_text_on, const int32_t* row_spk_on, float* v_out, void* stream);
+int echo_sample_euler_items_len(echo_ctx* ctx, const echo_sampler_params* p, const echo_sampler_item* items /* p->B entries */,
+                                const int32_t* item_start_pos /* host, p->B, may be NULL */, const int32_t* item_len /* host, p->B */,
+                                const float* x_init, float* latent_out, void* stream);
+
 /* inference.py:226-229 ae_decode -> autoencoder.py:1128-1132 DAC.decode_zq, one batch item:
  * latent (T, latent_size) fp32 -> wav (T * hop) fp32.
  * ECHO_BF16 context (ABI 8): the PCA inverse is evaluated in fp32 and rounded to bf16 once (inference.py:227-229), the decoder runs in bf16 and the
