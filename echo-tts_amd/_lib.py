@@ -136,6 +136,7 @@ SIGNATURES = {
     "echo_op_presplit_weights": (C.c_int, [vp, c_i64, c_i64, vp]),
     "echo_op_pack_rows": (C.c_int, [vp, C.c_int, c_i64, vp, C.c_int, c_i64, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     "echo_op_attention_bf16": (C.c_int, [C.POINTER(EchoAttnDesc), vp]),
+    "echo_op_attention_bf16_len": (C.c_int, [C.POINTER(EchoAttnDesc), vp, vp]),
     "echo_op_norm": (C.c_int, [C.c_int, C.c_int, vp, c_i64, vp, c_i64, C.c_int, C.c_int, C.c_float, vp, vp, vp]),
     "echo_op_headnorm_rope": (C.c_int, [C.c_int, vp, c_i64, c_i64, C.c_int, C.c_int, C.c_int, C.c_int, vp, c_i64, C.c_float,
                                         C.c_int, C.c_int, vp, C.c_int, C.c_int, vp]),

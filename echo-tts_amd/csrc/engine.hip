@@ -2744,9 +2744,11 @@ int echo_op_pack_rows(const void* src, int sdt, int64_t sld, void* dst, int ddt,
                       int swiglu_half, void* stream) {
   return op_status(launch_pack_rows(src, sdt, sld, dst, ddt, dld, rows, cols, dst_row0, swiglu_half, (hipStream_t)stream));
 }
-int echo_op_attention_bf16(const echo_attn_desc* d, void* stream) {
+// descriptor -> AttnArgs -> launch, shared by echo_op_attention_bf16 (qlen == nullptr) and echo_op_attention_bf16_len
+static int op_attention_bf16(const echo_attn_desc* d, const int32_t* qlen, void* stream) {
   AttnArgs a;
   memset(&a, 0, sizeof(a));
+  a.qlen = qlen;
   a.Q = (const bf16_t*)d->Q; a.q_ld = d->q_ld; a.q_row_stride = d->q_row_stride;
   a.O = (bf16_t*)d->O; a.o_ld = d->o_ld; a.o_row_stride = d->o_row_stride;
   a.G = (const bf16_t*)d->G; a.g_ld = d->g_ld; a.g_row_stride = d->g_row_stride;
@@ -2771,6 +2773,11 @@ int echo_op_attention_bf16(const echo_attn_desc* d, void* stream) {
     a.redo = rb.as<int>();
   }
   return op_status(launch_attention_bf16(a, (hipStream_t)stream));
+}
+int echo_op_attention_bf16(const echo_attn_desc* d, void* stream) { return op_attention_bf16(d, nullptr, stream); }
+int echo_op_attention_bf16_len(const echo_attn_desc* d, const int32_t* qlen_dev, void* stream) {
+  if (!d || !qlen_dev) { g_create_error = "echo_op_attention_bf16_len: null descriptor or length table"; return ECHO_ERR; }
+  return op_attention_bf16(d, qlen_dev, stream);
 }
 int echo_op_norm(int dtype, int mode, const void* x, int64_t ldx, void* y, int64_t ldy, int rows, int D, float eps, const void* w0,
                  const void* w1, void* stream) {

@@ -342,6 +342,11 @@ typedef struct {
   int g_activated;               /* ABI 6: G already holds bf16(sigmoid(gate)) (echo_gemm_desc.qkv_gate_act): the epilogue only multiplies */
 } echo_attn_desc;
 int echo_op_attention_bf16(const echo_attn_desc* d, void* stream);
+/* The same launch under a per-row length table (additive under ABI 8): qlen_dev[r] (device, d->rows entries) is the number of
+ * leading queries of row r that anybody reads.  A query block that starts at or beyond it is not computed: its O block comes back as zeros.
+ * The self segment's key counts are the caller's (the engine passes nkeys = qlen); K / Vt at padding positions must be finite.  A NULL
+ * table, causal, O8, prof or a per-key bias together with a table fail with a status and a message (echo_last_error(NULL)). */
+int echo_op_attention_bf16_len(const echo_attn_desc* d, const int32_t* qlen_dev, void* stream);
 
 int echo_op_norm(int dtype, int mode, const void* x, int64_t ldx, void* y, int64_t ldy, int rows, int D, float eps,
                  const void* w0, const void* w1, void* stream);

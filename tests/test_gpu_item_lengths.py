@@ -9,7 +9,8 @@ A call has B items and a row length S; item b owns the first len[b] tokens of it
 
 Which attention kernel runs: the switch ECHO_ATTN is read once per process, at the first launch; this module runs under the default, so the
 bf16 engine's joint attention is attn5_qlen_kernel (the length form of attn5_kernel) with attn_redo_kernel behind it.  attn_qlen_kernel (the
-form behind ECHO_ATTN=1) shares the padding decision and the zero-block writer with it and runs attn_kernel's body unchanged."""
+form behind ECHO_ATTN=1) runs the padding, stale-workspace and block-skipping tests of this module in a child process of
+tests/test_gpu_attention_len.py, which also holds both forms to an fp64 reference at kernel level."""
 import ctypes as C
 
 import pytest
