@@ -60,6 +60,11 @@ class EchoSamplerItem(C.Structure):
                 ("kv_scale", C.c_float), ("kv_max_layers", C.c_int), ("steps", C.POINTER(EchoStep))]
 
 
+class EchoDacTailItem(C.Structure):
+    """One stream of a batched tail decode (echo_dac_tail_item, added under ABI 8)."""
+    _fields_ = [("latent", vp), ("T", C.c_int32), ("first_frame", C.c_int32), ("drop_frames", C.c_int32), ("wav_out", vp)]
+
+
 class EchoGemmDesc(C.Structure):
     _fields_ = [("A", vp), ("W", vp), ("C", vp), ("C2", vp),
                 ("M", C.c_int), ("N", C.c_int), ("K", C.c_int), ("Npad", C.c_int),
@@ -159,6 +164,7 @@ SIGNATURES = {
     "echo_voice_bytes": (c_i64, [vp]),
     "echo_voice_destroy": (None, [vp]),
     "echo_dac_decode_tail": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_float, vp, vp]),
+    "echo_dac_decode_tail_items": (C.c_int, [vp, C.POINTER(EchoDacTailItem), C.c_int, C.c_float, vp]),
     "echo_workspace_bytes": (c_i64, [vp]),
     "echo_fp8_calibrate": (C.c_int, [vp, C.c_int]),
     "echo_fp8_calibration": (C.c_int, [vp, C.POINTER(C.c_float), C.c_int]),

@@ -448,6 +448,25 @@ class DAC:
                                                self._stream()), self._ctx)
         return out
 
+    @torch.no_grad()
+    def decode_latent_tails(self, items) -> list:
+        """The tails of several streams in ONE engine call (echo_dac_decode_tail_items).  items: [(latents (T, latent_size), first_frame,
+        drop_frames)].  Item i is `decode_latent_tail(latents, first_frame)` without its first drop_frames * hop samples; returns the list of
+        1-D waveforms ((T - first_frame - drop_frames) * hop samples each)."""
+        items = list(items)
+        n, hop = len(items), self.config.hop
+        tab = (L.EchoDacTailItem * max(n, 1))()
+        keep, outs = [], []
+        for i, (latent, first_frame, drop_frames) in enumerate(items):
+            lat = latent.to(self._device, torch.float32).contiguous()
+            T = int(lat.shape[0])
+            out = torch.empty((max(0, T - int(first_frame) - int(drop_frames)) * hop,), dtype=torch.float32, device=self._device)
+            keep.append(lat)
+            outs.append(out)
+            tab[i].latent, tab[i].T, tab[i].first_frame, tab[i].drop_frames, tab[i].wav_out = lat.data_ptr(), T, int(first_frame), int(drop_frames), out.data_ptr()
+        L.check(self._lib.echo_dac_decode_tail_items(self._ctx, tab, n, self._latent_scale, self._stream()), self._ctx)
+        return outs
+
     def conv_context_frames(self) -> int:
         """Latent frames of left context after which the causal convolutional stack (quantizer.upsample + Decoder,
         autoencoder.py:427-435, 971-998) no longer sees the start of its input: dwconv k7 per upsample stage, conv k7, per block
@@ -477,6 +496,24 @@ class DAC:
         return out
 
 
+
+
+def tail_requests(emitted, new_lengths, context):
+    """`DACStream.push`'s arithmetic, stated once: stream i has emitted[i] frames decoded so far and receives new_lengths[i] more; with `context`
+    frames of left context the decode of its new frames is the tail request (T, first_frame, drop_frames) = (emitted + new, max(0, emitted -
+    context), emitted - first_frame): the convolution stack re-decodes up to `context` frames in front of the new ones, and exactly those are
+    dropped.  `context` is one number or one per stream.  Pure host arithmetic."""
+    emitted, new_lengths = [int(e) for e in emitted], [int(n) for n in new_lengths]
+    ctxs = [int(context)] * len(emitted) if isinstance(context, int) else [int(c) for c in context]
+    if not (len(emitted) == len(new_lengths) == len(ctxs)):
+        raise ValueError("tail_requests: one emitted count, one new length and one context per stream")
+    out = []
+    for e, n, c in zip(emitted, new_lengths, ctxs):
+        if e < 0 or n < 1 or c < 0:
+            raise ValueError("tail_requests: emitted >= 0, new length >= 1 and context >= 0 expected")
+        f0 = max(0, e - c)
+        out.append((e + n, f0, e - f0))
+    return out
 
 
 class DACStream:
@@ -509,3 +546,37 @@ class DACStream:
         wav = wav[(self.emitted - f0) * self.ae.config.hop:]
         self.emitted = self.latents.shape[0]
         return wav.view(1, 1, -1)
+
+    @staticmethod
+    @torch.no_grad()
+    def push_many(streams, blocks) -> list:
+        """`push` for several streams in ONE engine call (`DAC.decode_latent_tails`): blocks[i] ((n_i, latent_size) or (1, n_i, latent_size))
+        goes to streams[i]; returns the list of (1, 1, n_i * hop) chunks.  Every stream's `latents` / `emitted` end up as after its own `push`.
+        ValueError: streams on different `DAC` objects, more than 32 streams, the same stream twice, an empty block, list lengths that differ."""
+        streams, blocks = list(streams), list(blocks)
+        if len(streams) != len(blocks):
+            raise ValueError("push_many: one block per stream expected")
+        if not streams:
+            return []
+        if len(streams) > 32:
+            raise ValueError("push_many: at most 32 streams per call")
+        if len({id(s) for s in streams}) != len(streams):
+            raise ValueError("push_many: the same stream appears twice")
+        ae = streams[0].ae
+        if any(s.ae is not ae for s in streams):
+            raise ValueError("push_many: the streams belong to different DAC objects (contexts)")
+        new = []
+        for b in blocks:
+            if b.dim() == 3:
+                if b.shape[0] != 1:
+                    raise ValueError("DACStream decodes one utterance; use one stream per batch item")
+                b = b[0]
+            if b.dim() != 2 or b.shape[0] < 1:
+                raise ValueError("push_many: an empty block")
+            new.append(b.to(ae.device, torch.float32))
+        reqs = tail_requests([s.emitted for s in streams], [b.shape[0] for b in new], [s.context for s in streams])
+        lats = [b if s.latents is None else torch.cat([s.latents, b], dim=0) for s, b in zip(streams, new)]
+        wavs = ae.decode_latent_tails([(lat, f0, drop) for lat, (_, f0, drop) in zip(lats, reqs)])
+        for s, lat in zip(streams, lats):      # state moves only once the call has succeeded
+            s.latents, s.emitted = lat, lat.shape[0]
+        return [w.view(1, 1, -1) for w in wavs]

@@ -328,6 +328,26 @@ template <typename E>
 hipError_t launch_conv_out_tanh(const E* x, long ldx, float* y, long T, int S, int C, int k, const E* w /*(k,C)*/,
                                 float bias, hipStream_t st);
 hipError_t launch_pca_prep(const float* lat, float* out, long ldo, long rows, int L, int Lpad, float scale, hipStream_t st);
+// ---- batched streaming tails (echo_dac_decode_tail_items): one table entry per stream, in the engine's slot order
+struct DacTailItem {
+  const float* lat;   // (T, latent) fp32, the stream's frames so far
+  float* wav;         // receives (T - f0 - drop) * samples-per-frame samples
+  int T, f0, drop, pad_;
+};
+// ragged PCA operand: row i * Tmax + t of `out` = lat_i[t] / scale for t < T_i, zeros behind (the caller's memory beyond T_i is never read)
+hipError_t launch_tail_pca_prep(const DacTailItem* tab, int n, int Tmax, float* out, long ldo, int L, int Lpad, float scale, hipStream_t st);
+// slot i (W rows of C) = rows f0_i .. T_i - 1 of item item0 + i of `front` ((items, Tmax, C) rows), zeros behind the item's own tail
+template <typename E>
+hipError_t launch_tail_gather(const E* front, int Tmax, int item0, const DacTailItem* tab, int n, int W, int C, E* dst, hipStream_t st);
+// left context of every slot of one decoder layer: `gap` elements at dst + i * pitch (elements), i < n.  real: the last `gap` elements of the flat
+// array [zeros | front rows 0 .. f0_i - 1 of item item0 + i] (what echo_dac_decode_tail's taps read in front of such an operand); else zeros
+template <typename E>
+hipError_t launch_tail_context(const E* front, int Tmax, int item0, const DacTailItem* tab, int n, long gap, int C, E* dst, long pitch, int real,
+                               hipStream_t st);
+// conv_out_tanh on n slots of S rows, `pitch` rows apart in x: slot i's rows [drop_i * rpf, (T_i - f0_i) * rpf) go to tab[i].wav, nothing else is written
+template <typename E>
+hipError_t launch_conv_out_tanh_items(const E* x, long ldx, long pitch, const DacTailItem* tab, int n, int S, int rpf, int C, int k,
+                                      const E* w /*(k,C)*/, float bias, hipStream_t st);
 hipError_t launch_presplit_w(float* w, long rows, long ld, hipStream_t st);
 hipError_t launch_snake_f32(const float* x, long ldx, float* y, long ldy, long rows, int C, const float* alpha, hipStream_t st);
 // encode path

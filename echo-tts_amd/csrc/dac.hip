@@ -171,6 +171,122 @@ __global__ void snake_kernel(const float* __restrict__ x, long ldx, float* __res
   y[r * ldy + c] = v + (1.0f / (a + 1e-9f)) * (sn * sn);
 }
 
+// ---- batched streaming tails
+// pca_prep_kernel on n items of different lengths, left-aligned in [n][Tmax] rows: the latent pointers come from the device table, rows at and
+// beyond T_i are written as zeros and the item's memory there is never read
+__global__ void tail_pca_prep_kernel(const DacTailItem* __restrict__ tab, int n, int Tmax, float* __restrict__ out, long ldo, int L, int Lpad,
+                                     float scale) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (long)n * Tmax * Lpad) return;
+  const long r = i / Lpad;
+  const int l = (int)(i - r * Lpad);
+  const int it = (int)(r / Tmax), t = (int)(r - (long)it * Tmax);
+  const DacTailItem d = tab[it];
+  out[r * ldo + l] = (l < L && t < d.T) ? d.lat[(long)t * L + l] / scale : 0.0f;
+}
+
+// 16-byte chunks: slot i, row w <- front row (item0 + i) * Tmax + f0_i + w while that is one of the item's own frames, zeros otherwise
+template <typename E>
+__global__ void tail_gather_kernel(const E* __restrict__ front, int Tmax, int item0, const DacTailItem* __restrict__ tab, int n, int W, int C,
+                                   E* __restrict__ dst) {
+  constexpr int EPC = 16 / (int)sizeof(E);
+  const int cpr = C / EPC;
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (long)n * W * cpr) return;
+  const long r = i / cpr;
+  const int c = (int)(i - r * cpr) * EPC;
+  const int s = (int)(r / W), w = (int)(r - (long)s * W);
+  const DacTailItem d = tab[s];
+  uint4 v = make_uint4(0u, 0u, 0u, 0u);
+  if (w < d.T - d.f0) v = *(const uint4*)(front + ((long)(item0 + s) * Tmax + d.f0 + w) * C + c);
+  *(uint4*)(dst + r * C + c) = v;
+}
+
+// the left context of slot s of one layer: `gap` elements at dst + s * pitch.  real: the last `gap` elements of the flat array [zeros | item
+// item0 + s's front rows 0 .. f0 - 1] - what echo_dac_decode_tail's taps find in front of an operand that starts f0 * C elements into the buffer
+// that holds the front's output; otherwise zeros.  16-byte chunks (gap, pitch and C are multiples of the chunk).
+template <typename E>
+__global__ void tail_context_kernel(const E* __restrict__ front, int Tmax, int item0, const DacTailItem* __restrict__ tab, int n, long gap, int C,
+                                    E* __restrict__ dst, long pitch, int real) {
+  constexpr int EPC = 16 / (int)sizeof(E);
+  const long per = gap / EPC;
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= per * n) return;
+  const int s = (int)(i / per);
+  const long g = (i - (long)s * per) * EPC;
+  const long flat = (long)tab[s].f0 * C - gap + g;
+  uint4 v = make_uint4(0u, 0u, 0u, 0u);
+  if (real && flat >= 0) v = *(const uint4*)(front + (long)(item0 + s) * Tmax * C + flat);
+  *(uint4*)(dst + (long)s * pitch + g) = v;
+}
+
+// conv_out_tanh_kernel for n slots (blockIdx.y) of S rows each, `pitch` rows apart: same lane assignment and summation order per output, so a
+// slot's samples have the bits of the single-item kernel.  Slot i owns rows [0, (T_i - f0_i) * rpf); its first drop_i * rpf samples are the
+// re-decoded context and are not written, the rest goes straight to the item's own buffer.
+template <typename E>
+__global__ void __launch_bounds__(256) conv_out_tanh_items_kernel(const E* __restrict__ x, long ldx, long pitch,
+                                                                  const DacTailItem* __restrict__ tab, int S, int rpf, int C, int k,
+                                                                  const E* __restrict__ w, float bias) {
+  typedef Vec4<E> V;
+  __shared__ float d[CO_ROWS][CO_KMAX];
+  const int R = CO_ROWS - (k - 1);                       // outputs per block
+  const DacTailItem item = tab[blockIdx.y];
+  const long own = (long)(item.T - item.f0) * rpf, nvalid = own < S ? own : S, skip = (long)item.drop * rpf;
+  const long t0 = (long)blockIdx.x * R;
+  if (t0 >= nvalid || t0 + R <= skip) return;            // block-uniform: nothing of this block is written
+  x += (long)blockIdx.y * pitch * ldx;
+  const int g = threadIdx.x >> 3, j = threadIdx.x & 7;
+  float4 wr[CO_KMAX][CO_NV];
+#pragma unroll
+  for (int kk = 0; kk < CO_KMAX; ++kk)
+#pragma unroll
+    for (int v = 0; v < CO_NV; ++v) {
+      const int c = (j + 8 * v) * 4;
+      float wv[4] = {0.f, 0.f, 0.f, 0.f};
+      if (kk < k && c < C) V::unpack(*(const typename V::raw*)(w + (long)kk * C + c), wv);
+      wr[kk][v] = make_float4(wv[0], wv[1], wv[2], wv[3]);
+    }
+#pragma unroll 1
+  for (int it = 0; it < CO_ROWS / 32; ++it) {
+    const int lr = it * 32 + g;
+    const long t = t0 - (k - 1) + lr;
+    float acc[CO_KMAX];
+#pragma unroll
+    for (int kk = 0; kk < CO_KMAX; ++kk) acc[kk] = 0.f;
+    if (t >= 0 && t < nvalid) {
+#pragma unroll
+      for (int v = 0; v < CO_NV; ++v) {
+        const int c = (j + 8 * v) * 4;
+        if (c < C) {
+          float xs[4];
+          V::unpack(*(const typename V::raw*)(x + t * ldx + c), xs);
+          const float4 xv = make_float4(xs[0], xs[1], xs[2], xs[3]);
+#pragma unroll
+          for (int kk = 0; kk < CO_KMAX; ++kk) {
+            acc[kk] = fmaf(xv.x, wr[kk][v].x, acc[kk]); acc[kk] = fmaf(xv.y, wr[kk][v].y, acc[kk]);
+            acc[kk] = fmaf(xv.z, wr[kk][v].z, acc[kk]); acc[kk] = fmaf(xv.w, wr[kk][v].w, acc[kk]);
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int kk = 0; kk < CO_KMAX; ++kk) {
+      float a = acc[kk];
+      a += __shfl_xor(a, 1, 64); a += __shfl_xor(a, 2, 64); a += __shfl_xor(a, 4, 64);
+      if (j == 0) d[lr][kk] = a;
+    }
+  }
+  __syncthreads();
+  const int i = threadIdx.x;
+  const long t = t0 + i;
+  if (i < R && t >= skip && t < nvalid) {
+    float a = bias;
+    for (int kk = 0; kk < k; ++kk)
+      if (t + kk - (k - 1) >= 0) a += d[i + kk][kk];
+    item.wav[t - skip] = Num<E>::rnd(tanhf(Num<E>::rnd(a)));
+  }
+}
+
 inline dim3 grid1d(long n, int bs = 256) { return dim3((unsigned)((n + bs - 1) / bs)); }
 
 }  // namespace
@@ -298,3 +414,37 @@ template hipError_t launch_dwconv_ln<bf16_t>(const bf16_t*, long, bf16_t*, long,
                                              const bf16_t*, float, hipStream_t);
 template hipError_t launch_conv_out_tanh<float>(const float*, long, float*, long, int, int, int, const float*, float, hipStream_t);
 template hipError_t launch_conv_out_tanh<bf16_t>(const bf16_t*, long, float*, long, int, int, int, const bf16_t*, float, hipStream_t);
+
+hipError_t launch_tail_pca_prep(const DacTailItem* tab, int n, int Tmax, float* out, long ldo, int L, int Lpad, float scale, hipStream_t st) {
+  hipLaunchKernelGGL(tail_pca_prep_kernel, grid1d((long)n * Tmax * Lpad), dim3(256), 0, st, tab, n, Tmax, out, ldo, L, Lpad, scale);
+  return hipGetLastError();
+}
+template <typename E>
+hipError_t launch_tail_gather(const E* front, int Tmax, int item0, const DacTailItem* tab, int n, int W, int C, E* dst, hipStream_t st) {
+  constexpr int EPC = 16 / (int)sizeof(E);
+  if (C % EPC || n < 1 || W < 1) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(tail_gather_kernel<E>, grid1d((long)n * W * (C / EPC)), dim3(256), 0, st, front, Tmax, item0, tab, n, W, C, dst);
+  return hipGetLastError();
+}
+template <typename E>
+hipError_t launch_tail_context(const E* front, int Tmax, int item0, const DacTailItem* tab, int n, long gap, int C, E* dst, long pitch, int real,
+                               hipStream_t st) {
+  constexpr int EPC = 16 / (int)sizeof(E);
+  if (C % EPC || gap % EPC || pitch % EPC || gap < EPC || n < 1 || ((uintptr_t)dst & 15)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(tail_context_kernel<E>, grid1d(gap / EPC * n), dim3(256), 0, st, front, Tmax, item0, tab, n, gap, C, dst, pitch, real);
+  return hipGetLastError();
+}
+template hipError_t launch_tail_context<float>(const float*, int, int, const DacTailItem*, int, long, int, float*, long, int, hipStream_t);
+template hipError_t launch_tail_context<bf16_t>(const bf16_t*, int, int, const DacTailItem*, int, long, int, bf16_t*, long, int, hipStream_t);
+template <typename E>
+hipError_t launch_conv_out_tanh_items(const E* x, long ldx, long pitch, const DacTailItem* tab, int n, int S, int rpf, int C, int k,
+                                      const E* w, float bias, hipStream_t st) {
+  if (C % 4 || C > 32 * CO_NV || k < 1 || k > CO_KMAX || (ldx & 3) || n < 1 || S < 1 || rpf < 1 || pitch < S) return hipErrorInvalidValue;
+  const int R = CO_ROWS - (k - 1);
+  hipLaunchKernelGGL(conv_out_tanh_items_kernel<E>, dim3((unsigned)((S + R - 1) / R), n), dim3(256), 0, st, x, ldx, pitch, tab, S, rpf, C, k, w, bias);
+  return hipGetLastError();
+}
+template hipError_t launch_tail_gather<float>(const float*, int, int, const DacTailItem*, int, int, int, float*, hipStream_t);
+template hipError_t launch_tail_gather<bf16_t>(const bf16_t*, int, int, const DacTailItem*, int, int, int, bf16_t*, hipStream_t);
+template hipError_t launch_conv_out_tanh_items<float>(const float*, long, long, const DacTailItem*, int, int, int, int, int, const float*, float, hipStream_t);
+template hipError_t launch_conv_out_tanh_items<bf16_t>(const bf16_t*, long, long, const DacTailItem*, int, int, int, int, int, const bf16_t*, float, hipStream_t);

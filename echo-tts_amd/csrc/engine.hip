@@ -197,6 +197,7 @@ struct EngineBase {
   virtual int voice_capture(struct VoiceSnap** out, hipStream_t st) = 0;
   virtual int voice_bind(const struct VoiceSnap* v, hipStream_t st) = 0;
   virtual int dac_decode_tail(const float* lat, int T, int f0, float scale, float* wav, hipStream_t st) = 0;
+  virtual int dac_decode_tail_items(const echo_dac_tail_item* items, int n, float scale, hipStream_t st) = 0;
   virtual size_t workspace_bytes() = 0;
   virtual int reserve_workspace(int B, int S, int Tt, int Ts, int T_dac) = 0;
   virtual int fp8_calibrate(int on) = 0;
@@ -272,7 +273,7 @@ struct Engine : EngineBase {
     for (auto& e : nk_ev) if (e) (void)hipEventDestroy(e);
     for (void* p : owned) (void)hipFree(p);
     for (DevBuf* b : all_bufs()) b->release();
-    b_gemm_ws.release(); b_tune_c.release(); b_flush.release(); b_sink.release();
+    b_gemm_ws.release(); b_tune_c.release(); b_flush.release(); b_sink.release(); b_tail_tab.release();
   }
 
   // ------------------------------------------------------------------ weights
@@ -2368,6 +2369,201 @@ struct Engine : EngineBase {
     return ECHO_OK;
   }
 
+  // ------------------------------------------------------------------ batched streaming tails (echo_dac_decode_tail_items)
+  // n streams, each with its own history length T_i and first frame f0_i, in one call.  The front runs once on [n][Tmax] left-aligned rows
+  // (the window transformer is causal: the zero-latent padding behind an item cannot reach its own rows).  The convolution stack runs once per
+  // layer for a GROUP of items: item i's frames f0_i.. sit in slot i of W frames (W = the group's longest tail), every taps-GEMM is launched
+  // with nbatch = slots and per-slot strides whose pitch leaves context rows in front of every slot - the causal left context of that slot, which
+  // no launch writes (edge tiles predicate on m < M or store to the sink) and which holds what the single call's taps read there (dac_tail_group).
+  DevBuf b_tail_tab;
+  static constexpr int TAIL_MAX_ITEMS = 32;
+  static constexpr long TAIL_GROUP_FRAMES = 640;      // a group fits the buffers of a one-utterance decode of this many frames
+  static constexpr long TAIL_Z0 = 8, TAIL_ZB = 64;    // context rows in front of a slot: first conv (k7: 6 rows; ConvTranspose: 1) | decoder blocks (k7 dilation 9: 54)
+  long dac_upf() const { long u = 1; for (int i = 0; i < cfg.dac_n_up; ++i) u *= cfg.dac_up_factors[i]; return u; }
+  // elements of the largest activation of a one-utterance decode (dac_run's sizing)
+  long dac_maxel(long frames) {
+    const long upf = dac_upf();
+    long maxel = frames * upf * std::max(cfg.dac_latent_dim * 4, cfg.dac_decoder_dim), rows = frames * upf;
+    for (auto& b : dblocks) { rows *= b.r; maxel = std::max(maxel, rows * b.co); }
+    return maxel;
+  }
+  // elements a group of n slots of W frames needs in each of b_dacA/B/C, context rows in front of the slots included
+  long tail_group_need(long n, long W) {
+    const long C = cfg.dac_latent_dim, Wu = W * dac_upf();
+    long need = std::max(n * Wu * 4 * C, n * (Wu + TAIL_Z0) * std::max<long>(C, cpad(cfg.dac_decoder_dim))), rows = Wu;
+    for (auto& b : dblocks) { rows *= b.r; need = std::max(need, n * (rows + TAIL_ZB) * b.co); }
+    return need;
+  }
+  int dac_decode_tail_items(const echo_dac_tail_item* items, int n, float latent_scale, hipStream_t st) override {
+    if (!dac_ready) return fail("echo_finalize_dac was not called");
+    if (!pca_set) return fail("echo_set_pca was not called");
+    if (!items) return fail("dac_decode_tail_items: null item table");
+    if (n < 1 || n > TAIL_MAX_ITEMS) return fail("dac_decode_tail_items: n = " + std::to_string(n) + " is outside 1.." + std::to_string(TAIL_MAX_ITEMS));
+    if (!ae_rope) return fail("ae rope table missing");
+    int Tmax = 0;
+    for (int i = 0; i < n; ++i) {
+      const echo_dac_tail_item& it = items[i];
+      const std::string who = "dac_decode_tail_items: item " + std::to_string(i) + ": ";
+      if (!it.latent || !it.wav_out) return fail(who + "null pointer");
+      if (it.T < 1) return fail(who + "T must be at least 1");
+      if (it.T > ae_rope_npos) return fail(who + "T = " + std::to_string(it.T) + " is beyond the ae rope table (" + std::to_string(ae_rope_npos) + " positions)");
+      if (it.first_frame < 0 || it.first_frame >= it.T) return fail(who + "first_frame = " + std::to_string(it.first_frame) + " is outside [0, T)");
+      if (it.drop_frames < 0 || it.drop_frames >= it.T - it.first_frame)
+        return fail(who + "drop_frames = " + std::to_string(it.drop_frames) + " is outside [0, T - first_frame)");
+      Tmax = std::max(Tmax, (int)it.T);
+    }
+    // slot order: longest tail first (stable), so that a group's first item sets its slot length
+    std::vector<int> order(n);
+    for (int i = 0; i < n; ++i) order[i] = i;
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return items[a].T - items[a].first_frame > items[b].T - items[b].first_frame; });
+    std::vector<DacTailItem> tab(n);
+    for (int i = 0; i < n; ++i) {
+      const echo_dac_tail_item& it = items[order[i]];
+      tab[i] = DacTailItem{it.latent, it.wav_out, it.T, it.first_frame, it.drop_frames, 0};
+    }
+    const int C = cfg.dac_latent_dim, nh = cfg.dac_post_heads, hd = cfg.dac_post_head_dim, ff = cfg.dac_post_ffn;
+    if (profiling) {
+      for (auto& e : ev) if (!e) CK(hipEventCreate(&e));
+      gemm_events_used = 0;
+      CK(hipEventRecord(ev[0], st));
+    }
+    CK(b_tail_tab.reserve(TAIL_MAX_ITEMS * sizeof(DacTailItem)));
+    CK(stage_items.push(tab.data(), (size_t)n * sizeof(DacTailItem), b_tail_tab.p, st));
+    const DacTailItem* tab_dev = b_tail_tab.as<DacTailItem>();
+    // ---- ragged front: PCA inverse, post_module transformer, final norm on n * Tmax rows (dac_front_batch without quantizer.upsample)
+    const long R = (long)n * Tmax, Tp = rup(R, 128);
+    CK(b_dfx.reserve((size_t)(Tp + 128) * C * sizeof(T)));
+    CK(b_dfs.reserve((size_t)(Tp + 128) * (long)(C + ff) * sizeof(T)));
+    CK(b_dfu.reserve((size_t)(Tp + 128) * C * sizeof(T)));
+    CK(b_dfn.reserve((size_t)(Tp + 128) * C * sizeof(T)));
+    CK(b_dmisc.reserve((size_t)Tp * (pca_kpad + (DAC_BF16 ? C : 0)) * sizeof(float)));
+    T* x = b_dfx.as<T>();
+    {
+      float* prep = b_dmisc.as<float>();
+      CK(launch_tail_pca_prep(tab_dev, n, Tmax, prep, pca_kpad, cfg.latent_size, pca_kpad, latent_scale, st));
+      float* z;
+      if constexpr (DAC_BF16) z = prep + Tp * pca_kpad; else z = x;
+      GemmArgs g = FG(prep, pca_kpad, pca_w, pca_kpad, z, C, R, C, pca_kpad);
+      g.bias = pca_b;
+      CKI(frun<float>(g, st));
+      if constexpr (DAC_BF16) CK(launch_convert_from_f32<T>(z, C, x, C, (int)R, C, C, st));
+    }
+    CKI(dac_transformer<T>(dpost, x, Tmax, C, nh, hd, ff, cfg.dac_post_window, b_dfs.as<T>(), b_dfu.as<T>(), st, n));
+    CK(launch_norm<T>(NORM_AE_RMS, x, C, b_dfn.as<T>(), C, (int)R, C, cfg.dac_norm_eps, dpost_norm, nullptr, st));
+    // ---- groups: as many slots as the buffers of a TAIL_GROUP_FRAMES-frame decode hold; a single longer item is its own group
+    for (int g0 = 0; g0 < n;) {
+      const long W = tab[g0].T - tab[g0].f0;
+      const long cap = dac_maxel(TAIL_GROUP_FRAMES);
+      int ng = 1;
+      while (g0 + ng < n && (ng + 1) * W <= TAIL_GROUP_FRAMES && tail_group_need(ng + 1, W) <= cap) ++ng;
+      CKI(dac_tail_group(tab_dev + g0, g0, ng, (int)W, b_dfn.as<T>(), Tmax, st));
+      g0 += ng;
+    }
+    if (profiling) {     // per-item averages, as dac_decode_batch reports them
+      CK(hipEventRecord(ev[2], st));
+      CK(hipEventSynchronize(ev[2]));
+      CK(hipEventElapsedTime(&prof.ms_total, ev[0], ev[2]));
+      collect_gemm_times();
+      prof.ms_total /= n; prof.ms_mod = 0.f; prof.ms_steps = prof.ms_total; prof.ms_gemm_sum /= n;
+    }
+    return ECHO_OK;
+  }
+  // quantizer.upsample and the decoder for one group: n slots of W frames, slot i = frames f0_i.. of item item0 + i of `front` ((items, Tmax, C))
+  int dac_tail_group(const DacTailItem* tab_dev, int item0, int n, int W, const T* front, int Tmax, hipStream_t st) {
+    const int C = cfg.dac_latent_dim;
+    const long upf = dac_upf(), PADF = dac_padf();
+    const size_t bytes = (size_t)(tail_group_need(n, W) + PADF + 128L * 4 * C) * sizeof(T);
+    CK(b_dacA.reserve(bytes)); CK(b_dacB.reserve(bytes)); CK(b_dacC.reserve(bytes));
+    T *bufY = b_dacA.as<T>() + PADF, *bufS = b_dacB.as<T>() + PADF, *bufU = b_dacC.as<T>() + PADF;
+    // the slots, contiguous: quantizer.upsample has no tap that leaves an item (1-tap GEMMs; dwconv_ln restarts per `per_item` rows)
+    T *cur = bufS, *other = bufY, *third = bufU;
+    CK(launch_tail_gather<T>(front, Tmax, item0, tab_dev, n, W, C, cur, st));
+    long per_item = W;
+    for (auto& U : dups) {
+      const long rows = (long)n * per_item;
+      { GemmArgs g = FG(cur, C, U.w, C, other, (long)U.f * C, rows, U.f * C, C); g.bias = U.b; g.vec_mod = C; CKI(frun<T>(g, st)); }
+      per_item *= U.f;
+      const long rows2 = (long)n * per_item;
+      CK(launch_dwconv_ln(other, C, cur, C, (int)rows2, (int)per_item, C, U.dw, U.db, U.lnw, U.lnb, 1e-6f, st));
+      { GemmArgs g = FG(cur, C, U.p1w, C, third, 4L * C, rows2, 4 * C, C); g.bias = U.p1b; g.act = 2; CKI(frun<T>(g, st)); }
+      { GemmArgs g = FG(third, 4L * C, U.p2w, 4L * C, other, C, rows2, C, 4 * C); g.bias = U.p2b; g.colscale = U.gamma; g.res = other; g.ldres = C; CKI(frun<T>(g, st)); }
+      std::swap(cur, other);
+    }
+    // ---- decoder: slot i of a layer with `rows` rows of c channels starts at buf + Z * c + i * (rows + Z) * c; the Z rows in front of EVERY
+    // slot (the first included) are its left context and no launch writes them.  What they hold is what echo_dac_decode_tail's taps find in
+    // front of the same operand, so that an item equals its single call in every sample, the undropped ones right behind first_frame too:
+    //   - the buffer the single call enters the decoder with (X here: the first conv's input, then the Snake output of blocks 0, 2, ..) is,
+    //     with an even number of upsample stages, a pointer first_frame * C elements INTO the buffer that holds the front's output.  The
+    //     elements in front of it are the item's own front rows 0 .. first_frame - 1, flat, behind the buffer's zero padding, and every tap
+    //     that reaches in front of row 0 reads them in ITS channel layout.  launch_tail_context writes that flat tail (item i's rows only);
+    //   - every other operand starts at a buffer's base: zeros in front.
+    // b_dacA/B/C are re-used by layers of different geometry, so each geometry's context rows are written before the layer that reads them.
+    const int ctx_real = dups.size() % 2 == 0 ? 1 : 0;
+    long rows = per_item;
+    T *X = other, *Y = cur, *S = third, *Uu = nullptr;
+    auto context = [&](T* buf, long rws, long Z, long c) -> hipError_t {
+      return launch_tail_context<T>(front, Tmax, item0, tab_dev, n, Z * c, C, buf, (rws + Z) * c, buf == X ? ctx_real : 0, st);
+    };
+    CK(context(X, rows, TAIL_Z0, C));
+    CK(hipMemcpy2DAsync(X + TAIL_Z0 * C, (size_t)(rows + TAIL_Z0) * C * sizeof(T), cur, (size_t)rows * C * sizeof(T), (size_t)rows * C * sizeof(T), n,
+                        hipMemcpyDeviceToDevice, st));
+    long Zin = TAIL_Z0;
+    {
+      const int ch = cpad(cfg.dac_decoder_dim);
+      CK(context(S, rows, TAIL_Z0, ch));      // the ConvTranspose of block 0 reads one row in front of each slot of S
+      GemmArgs g = FG(X + TAIL_Z0 * C, C, dconv0_w, 7L * C, Y + TAIL_Z0 * ch, ch, rows, ch, C);
+      g.w_presplit = !DAC_BF16 && dac_split3;
+      g.taps = 7; g.tap_base = -6; g.tap_shift = 1; g.bias = dconv0_b;
+      g.store_main = 0; g.C2 = S + TAIL_Z0 * ch; g.snake_alpha = dblocks[0].alpha;
+      g.nbatch = n; g.a_bo = (rows + TAIL_Z0) * C; g.c_bo = (rows + TAIL_Z0) * ch;
+      CKI(frun<T>(g, st));
+      Uu = X;
+    }
+    for (size_t bi = 0; bi < dblocks.size(); ++bi) {
+      DacBlock& Bk = dblocks[bi];
+      const long pin = rows + Zin, pout = rows * Bk.r + TAIL_ZB;      // slot pitch in rows: input / output geometry of this block
+      const long oin = Zin * Bk.ci, off = TAIL_ZB * Bk.co;            // elements in front of slot 0
+      {
+        // Uu becomes this block's S (the buffer its k7 convs read with taps): its context rows in the NEW geometry are written before the
+        // ConvTranspose fills the slots; nothing writes them afterwards
+        CK(context(Uu, rows * Bk.r, TAIL_ZB, Bk.co));
+        GemmArgs g = FG(S + oin, Bk.ci, Bk.wt, 2L * Bk.ci, Y + off, (long)Bk.r * Bk.co, rows, Bk.r * Bk.co, Bk.ci);
+        g.w_presplit = !DAC_BF16 && dac_split3;
+        g.taps = 2; g.tap_base = -1; g.tap_shift = 1; g.bias = Bk.bt; g.vec_mod = Bk.co;
+        g.C2 = Uu + off; g.snake_alpha = Bk.ru[0].a0;
+        g.nbatch = n; g.a_bo = pin * Bk.ci; g.c_bo = pout * Bk.co;
+        CKI(frun<T>(g, st));
+        rows *= Bk.r; Zin = TAIL_ZB;
+        std::swap(S, Uu);
+      }
+      const long sb = pout * Bk.co;
+      const int dil[3] = {1, 3, 9};
+      for (int j = 0; j < 3; ++j) {
+        DacRU& ru = Bk.ru[j];
+        {
+          GemmArgs g = FG(S + off, Bk.co, ru.w7, 7L * Bk.co, Uu + off, Bk.co, rows, Bk.co, Bk.co);
+          g.w_presplit = !DAC_BF16 && dac_split3;
+          g.taps = 7; g.tap_base = -6 * dil[j]; g.tap_shift = dil[j]; g.bias = ru.b7;
+          g.store_main = 0; g.C2 = Uu + off; g.snake_alpha = ru.a1;
+          g.nbatch = n; g.a_bo = sb; g.c_bo = sb;
+          CKI(frun<T>(g, st));
+        }
+        {
+          const T* next_alpha = j < 2 ? Bk.ru[j + 1].a0 : (bi + 1 < dblocks.size() ? dblocks[bi + 1].alpha : dfinal_alpha);
+          GemmArgs g = FG(Uu + off, Bk.co, ru.w1, Bk.co, Y + off, Bk.co, rows, Bk.co, Bk.co);
+          g.w_presplit = !DAC_BF16 && dac_split3;
+          g.bias = ru.b1; g.res = Y + off; g.ldres = Bk.co;
+          g.store_main = j < 2 ? 1 : 0; g.C2 = S + off; g.snake_alpha = next_alpha;
+          g.nbatch = n; g.a_bo = sb; g.c_bo = sb; g.res_bo = sb;
+          CKI(frun<T>(g, st));
+        }
+      }
+    }
+    const int cl = cpad(cfg.dac_decoder_dim >> cfg.dac_n_rates);
+    CK(launch_conv_out_tanh_items(S + Zin * cl, cl, rows + Zin, tab_dev, n, (int)rows, (int)(rows / W), cl, 7, dout_w, dout_b, st));
+    return ECHO_OK;
+  }
+
   int dac_run(const float* lat, const float* zq, int Tn, float latent_scale, float* wav, hipStream_t st, int f0 = 0, const T* front = nullptr) {
     if (!dac_ready) return fail("echo_finalize_dac was not called");
     if (!ae_rope || Tn > ae_rope_npos) return fail("ae rope table missing or too short");
@@ -2680,6 +2876,9 @@ void echo_voice_destroy(echo_voice* voice) {
 }
 int echo_dac_decode_tail(echo_ctx* ctx, const float* latent, int T, int first_frame, float latent_scale, float* wav_out, void* stream) {
   return ctx ? ctx->eng->dac_decode_tail(latent, T, first_frame, latent_scale, wav_out, (hipStream_t)stream) : ECHO_ERR;
+}
+int echo_dac_decode_tail_items(echo_ctx* ctx, const echo_dac_tail_item* items, int n, float latent_scale, void* stream) {
+  return ctx ? ctx->eng->dac_decode_tail_items(items, n, latent_scale, (hipStream_t)stream) : ECHO_ERR;
 }
 int64_t echo_workspace_bytes(echo_ctx* ctx) { return ctx ? (int64_t)ctx->eng->workspace_bytes() : 0; }
 int echo_reserve_workspace(echo_ctx* ctx, int B, int S, int Tt, int Ts, int T_dac) {

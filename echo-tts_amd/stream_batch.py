@@ -14,8 +14,11 @@ Mixed block sizes (`StreamBatcher(mix_block_sizes=True)`, `plan_stream_step_mixe
 the largest block size among its streams; a shorter block rides along as a padded row with its own length (`echo_sample_euler_items_len`).
 `max_pad_fraction` bounds the share of padded tokens a call may carry.
 
-Not here: a captured text KV, batched DAC tail decode (decode stays per stream, `DACStream`), incremental prefix encoding, mixed step
-counts inside one call (streams are grouped by them)."""
+Batched decode (`StreamBatcher(batch_decode=True)`): `step_audio()` hands the step's new blocks to ONE `DACStream.push_many` call
+(`echo_dac_decode_tail_items`: the tails of all streams share the decoder front and every convolution launch) instead of one `push` per
+stream; continuation prefixes are pushed first, in one call of their own.  Off by default (DESIGN.md 3.13 has the measured A/B).
+
+Not here: a captured text KV, incremental prefix encoding, mixed step counts inside one call (streams are grouped by them)."""
 from __future__ import annotations
 
 from dataclasses import dataclass, field
@@ -140,12 +143,15 @@ class StreamBatcher:
     `handler.synthesize_many` takes it.  `open(speaker_voice=)` names one, passes a captured batch-1 `VoiceHandle`, or None (no speaker).
 
     `mix_block_sizes=True`: streams whose next blocks differ in size share a call (`plan_stream_step_mixed`, bounded by `max_pad_fraction`);
-    the default keeps one call per (block_size, num_steps)."""
+    the default keeps one call per (block_size, num_steps).
+
+    `batch_decode=True`: `step_audio()` decodes the step's blocks in one `DACStream.push_many` call instead of one `push` per stream."""
 
     def __init__(self, model, fish_ae, pca_state, voices=None, max_batch: int = 24, mix_block_sizes: bool = False,
-                 max_pad_fraction: Optional[float] = None):
+                 max_pad_fraction: Optional[float] = None, batch_decode: bool = False):
         from .handler import VoiceCache
         self.model, self.fish_ae, self.pca_state = model, fish_ae, pca_state
+        self.batch_decode = bool(batch_decode)
         self.max_batch = max(1, min(int(max_batch), MAX_ITEMS))
         self.mix_block_sizes, self.max_pad_fraction = bool(mix_block_sizes), max_pad_fraction
         self._cache = voices if isinstance(voices, VoiceCache) else VoiceCache()
@@ -315,6 +321,8 @@ class StreamBatcher:
         """`step()`, then each new block through its stream's own `DACStream` (batch 1): [(id, waveform chunk (1, 1, block_size * hop))].
         The concatenated chunks of a stream equal `ae_decode` of its final latent."""
         from .autoencoder import DACStream
+        if self.batch_decode:
+            return self._step_audio_batched()
         out = []
         for sid, start, block in self._step():
             s = self._streams[sid]
@@ -327,12 +335,34 @@ class StreamBatcher:
         return out
 
 
+    def _step_audio_batched(self) -> List[Tuple[int, torch.Tensor]]:
+        """`step_audio` with one engine call for the step's decodes: the continuation prefixes of streams that decode for the first time go
+        through one `push_many` (their audio exists already: only the decoder context is needed), the new blocks through a second one."""
+        from .autoencoder import DACStream
+        got = self._step()
+        if not got:
+            self._reap()
+            return []
+        rows = [self._streams[sid] for sid, _, _ in got]
+        fresh = []
+        for s, (_, start, _) in zip(rows, got):
+            if s.dec is None:
+                s.dec = DACStream(self.fish_ae, self.pca_state)
+                if start > 0:
+                    fresh.append((s.dec, s.prefix[:start]))
+        if fresh:
+            DACStream.push_many([d for d, _ in fresh], [p for _, p in fresh])
+        chunks = DACStream.push_many([s.dec for s in rows], [block[0] for _, _, block in got])
+        self._reap()
+        return [(sid, chunk) for (sid, _, _), chunk in zip(got, chunks)]
+
+
 def stream_audio_many(model, fish_ae, pca_state, requests: Sequence[dict], voices=None, max_batch: int = 24, mix_block_sizes: bool = False,
-                      max_pad_fraction: Optional[float] = None) -> Iterator[Tuple[int, torch.Tensor]]:
+                      max_pad_fraction: Optional[float] = None, batch_decode: bool = False) -> Iterator[Tuple[int, torch.Tensor]]:
     """Generator over a list of requests (dicts with the keyword arguments of `StreamBatcher.open`): opens them all and yields
-    `(request index, waveform chunk)` block by block until every stream is done.  `mix_block_sizes` / `max_pad_fraction`: `StreamBatcher`."""
+    `(request index, waveform chunk)` block by block until every stream is done.  `mix_block_sizes` / `max_pad_fraction` / `batch_decode`: `StreamBatcher`."""
     sb = StreamBatcher(model, fish_ae, pca_state, voices=voices, max_batch=max_batch, mix_block_sizes=mix_block_sizes,
-                       max_pad_fraction=max_pad_fraction)
+                       max_pad_fraction=max_pad_fraction, batch_decode=batch_decode)
     index = {sb.open(**dict(r)): i for i, r in enumerate(requests)}
     while sb.open_ids:
         for sid, chunk in sb.step_audio():

@@ -261,6 +261,26 @@ int echo_dac_decode_batch(echo_ctx* ctx, const float* latent, int B, int T, floa
  * samples.  Samples further than the stack's receptive field (< 10 frames) behind first_frame equal the
  * whole-utterance decode; the caller (DACStream in autoencoder.py) discards that context.  ECHO_BF16 context: as echo_dac_decode. */
 int echo_dac_decode_tail(echo_ctx* ctx, const float* latent, int T, int first_frame, float latent_scale, float* wav_out, void* stream);
+/* The tails of n open streams in one call (additive under ABI 8).  Item i means echo_dac_decode_tail(latent, T, first_frame, ...)
+ * followed by dropping the first drop_frames * hop samples (the re-decoded context): the front sees all T frames of that item and no other
+ * item's, the convolution stack frames first_frame.. with the single call's left context at every layer, wav_out receives the remaining samples and nothing
+ * else is written.  The front runs once on the items' stacked rows, the convolution stack once per layer for a group of items (groups are
+ * formed so that the decode buffers stay those of one 640-frame utterance).
+ *   - fp32: an item agrees with its single call up to the fp32 summation order of the row-wise GEMMs (other M, other tile plans).
+ *   - ECHO_BF16: same schedule; equal bits are NOT claimed for ragged groups (DESIGN.md 3.13 names the kernel), the distance stays inside
+ *     half the bf16 decoder's own distance to fp32.
+ *   - in front of first_frame every layer sees what echo_dac_decode_tail's taps see there (rows of the item's own front output or zeros,
+ *     DESIGN.md 3.13), so the samples right behind a first_frame > 0 equal the single call's as well; DACStream drops them either way.
+ *   - an item's samples do not depend on the other items' contents; the caller's memory behind row T of a latent is never read.
+ * Fails (non-zero, echo_last_error; nothing is queued, the context stays usable) on n outside 1..32, first_frame outside [0, T),
+ * drop_frames outside [0, T - first_frame), T beyond the AE RoPE table, a missing echo_finalize_dac / echo_set_pca. */
+typedef struct {
+  const float* latent;     /* device, (T, latent_size) fp32: ALL frames of this stream so far */
+  int32_t T, first_frame;  /* the convolution stack runs on frames first_frame .. T-1 */
+  int32_t drop_frames;     /* leading frames of the tail whose samples are not written (the context) */
+  float* wav_out;          /* device, receives (T - first_frame - drop_frames) * hop samples */
+} echo_dac_tail_item;
+int echo_dac_decode_tail_items(echo_ctx* ctx, const echo_dac_tail_item* items /* host, n */, int n, float latent_scale, void* stream);
 /* inference.py:86-99 PCAState: w = pca_components transposed, (dac_latent_dim, latent_size) row-major fp32; mean (dac_latent_dim).
  * The operands stay fp32 in an ECHO_BF16 context as well: the reference computes the PCA inverse in fp32 whatever the AE dtype. */
 int echo_set_pca(echo_ctx* ctx, const float* w, const float* mean, int on_device, void* stream);
