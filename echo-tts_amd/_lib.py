@@ -159,6 +159,9 @@ SIGNATURES = {
                                        C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), vp, vp]),
     "echo_sample_euler_items_len": (C.c_int, [vp, C.POINTER(EchoSamplerParams), C.POINTER(EchoSamplerItem), C.POINTER(C.c_int32),
                                               C.POINTER(C.c_int32), vp, vp, vp]),
+    "echo_sample_euler_items_steps": (C.c_int, [vp, C.POINTER(EchoSamplerParams), C.POINTER(EchoSamplerItem), C.POINTER(C.c_int32),
+                                                C.POINTER(C.c_int32), C.POINTER(C.c_int32), vp, vp, vp]),
+    "echo_debug_item_steps_ignore_done": (C.c_int, [vp, C.c_int]),
     "echo_scale_speaker_kv_items": (C.c_int, [vp, C.POINTER(C.c_float), C.POINTER(C.c_int32), C.c_int, vp]),
     "echo_voice_bind_items": (C.c_int, [vp, C.POINTER(vp), C.c_int, vp]),
     "echo_voice_bytes": (c_i64, [vp]),

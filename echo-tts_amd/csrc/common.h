@@ -253,6 +253,7 @@ struct EulerItem {
   int has_cfg; float s_text, s_spk;
   int rescale; float r_inv1mt, r_ratio, r_1mt;
   float dt;
+  int done;                 // per-utterance step counts: the item finished at an earlier iteration; read by the *_steps kernels only
 };
 struct EulerItemsArgs {
   float* x; const void* v; long ldv; void* xin; long ld_xin;      // as EulerArgs
@@ -272,6 +273,11 @@ struct EulerItemsLenArgs {
 };
 // init: x = x0 * init_scale for valid tokens, 0 for padding.  step: euler_items_kernel's arithmetic for valid tokens; padding keeps x = 0.
 template <typename T> hipError_t launch_euler_items_len(const EulerItemsLenArgs& e, hipStream_t st);
+// Per-utterance step counts: the two launches above for a table whose entries carry `done`.  An item with done == 0 gets
+// their arithmetic, operation for operation; an item with done != 0 keeps x as it is (no store to x at all) and only has the next
+// forward's input staged from it.  The init launch is theirs.
+template <typename T> hipError_t launch_euler_items_steps(const EulerItemsArgs& e, hipStream_t st);
+template <typename T> hipError_t launch_euler_items_steps_len(const EulerItemsLenArgs& e, hipStream_t st);
 // xin[(r * S + s)][l < L] = s < len[r % B] ? x[(r * S + s)][l] : 0   (x, xin of T; the columns L.. of xin stay as they are: zero)
 template <typename T> hipError_t launch_stage_x_len(const T* x, int L, T* xin, long ld_xin, int rows, int B, int S, const int* len, hipStream_t st);
 // y[(r * S + s)][l < cols] = s < len[r % B] ? float(x[(r * S + s)][l]) : 0

@@ -387,6 +387,60 @@ __global__ void euler_items_len_kernel(const EulerItemsLenArgs p) {
   T* xin = (T*)e.xin;
   for (int r = 0; r < e.R_next; ++r) xin[(r * bs + tok) * e.ld_xin + l] = Num<T>::st(x);
 }
+// Per-utterance step counts: iteration i of the call is past the last step of an item whose entry carries `done`.  Such an
+// item's x is loaded only to stage the next forward's input (the layout stays rectangular, its rows are computed and nobody reads them) and
+// is NOT stored: x_t keeps the bits of the item's last step.  Every other item takes euler_items_kernel's path, operation for operation.
+template <typename T>
+__global__ void euler_items_steps_kernel(const EulerItemsArgs e) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long n = (long)e.B * e.S * e.L;
+  if (i >= n) return;
+  const long tok = i / e.L;
+  const int l = (int)(i - tok * e.L);
+  const int item = (int)(tok / e.S);
+  const long bs = (long)e.B * e.S;
+  float x = e.x[i];
+  if (e.init) {
+    const float s = e.init_scale[item];
+    if (s != 1.0f) x = __fmul_rn(x, s);
+    e.x[i] = x;
+  } else if (!e.items[item].done) {
+    x = euler_item_update<T>(e, item, tok, l, bs, x);
+    e.x[i] = x;
+  }
+  T* xin = (T*)e.xin;
+  for (int r = 0; r < e.R_next; ++r) xin[(r * bs + tok) * e.ld_xin + l] = Num<T>::st(x);
+}
+// The length form: euler_items_len_kernel for an item that still runs; a finished item's x (0 at its padding since the init launch) is staged, not stored.
+template <typename T>
+__global__ void euler_items_steps_len_kernel(const EulerItemsLenArgs p) {
+  const EulerItemsArgs& e = p.a;
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long n = (long)e.B * e.S * e.L;
+  if (i >= n) return;
+  const long tok = i / e.L;
+  const int l = (int)(i - tok * e.L);
+  const int item = (int)(tok / e.S);
+  const long bs = (long)e.B * e.S;
+  float x;
+  if (!e.init && e.items[item].done) {
+    x = e.x[i];
+  } else {
+    x = 0.0f;
+    if ((int)(tok - (long)item * e.S) < p.len[item]) {
+      if (e.init) {
+        x = p.x0[i];
+        const float s = e.init_scale[item];
+        if (s != 1.0f) x = __fmul_rn(x, s);
+      } else {
+        x = euler_item_update<T>(e, item, tok, l, bs, e.x[i]);
+      }
+    }
+    e.x[i] = x;
+  }
+  T* xin = (T*)e.xin;
+  for (int r = 0; r < e.R_next; ++r) xin[(r * bs + tok) * e.ld_xin + l] = Num<T>::st(x);
+}
 template <typename T>
 __global__ void stage_x_len_kernel(const T* __restrict__ x, int L, T* __restrict__ xin, long ld_xin, long n, int B, int S, const int* __restrict__ len) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -818,6 +872,17 @@ template <typename T> hipError_t launch_euler_items_len(const EulerItemsLenArgs&
   hipLaunchKernelGGL(euler_items_len_kernel<T>, grid1d((long)e.B * e.S * e.L), dim3(256), 0, st, p);
   return hipGetLastError();
 }
+template <typename T> hipError_t launch_euler_items_steps(const EulerItemsArgs& e, hipStream_t st) {
+  if (!e.x || !e.xin || (e.init ? !e.init_scale : (!e.items || !e.v)) || e.B < 1 || e.S < 1 || e.L < 1) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(euler_items_steps_kernel<T>, grid1d((long)e.B * e.S * e.L), dim3(256), 0, st, e);
+  return hipGetLastError();
+}
+template <typename T> hipError_t launch_euler_items_steps_len(const EulerItemsLenArgs& p, hipStream_t st) {
+  const EulerItemsArgs& e = p.a;
+  if (!e.x || !e.xin || !p.len || (e.init ? (!e.init_scale || !p.x0) : (!e.items || !e.v)) || e.B < 1 || e.S < 1 || e.L < 1) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(euler_items_steps_len_kernel<T>, grid1d((long)e.B * e.S * e.L), dim3(256), 0, st, p);
+  return hipGetLastError();
+}
 template <typename T>
 hipError_t launch_stage_x_len(const T* x, int L, T* xin, long ld_xin, int rows, int B, int S, const int* len, hipStream_t st) {
   if (!x || !xin || !len || L < 1 || ld_xin < L || rows < 1 || B < 1 || S < 1) return hipErrorInvalidValue;
@@ -963,6 +1028,8 @@ hipError_t launch_mask_to_bias(const uint8_t* mask, float* bias, long n, hipStre
   template hipError_t launch_euler<T>(const EulerArgs&, hipStream_t);                                                        \
   template hipError_t launch_euler_items<T>(const EulerItemsArgs&, hipStream_t);                                             \
   template hipError_t launch_euler_items_len<T>(const EulerItemsLenArgs&, hipStream_t);                                      \
+  template hipError_t launch_euler_items_steps<T>(const EulerItemsArgs&, hipStream_t);                                       \
+  template hipError_t launch_euler_items_steps_len<T>(const EulerItemsLenArgs&, hipStream_t);                                \
   template hipError_t launch_stage_x_len<T>(const T*, int, T*, long, int, int, int, const int*, hipStream_t);                \
   template hipError_t launch_convert_to_f32_len<T>(const T*, long, float*, long, int, int, int, int, const int*, hipStream_t); \
   template hipError_t launch_scale_kv_items<T>(T*, long, T*, long, int, int, int, const KvItemScales&, hipStream_t);         \

@@ -194,6 +194,7 @@ struct EngineBase {
   virtual int set_pca_encode(const float* w, const float* bias, float scale, int on_device, hipStream_t st) = 0;
   virtual int debug_get_kv(int which, int layer, float* k, float* v, int* B, int* T) = 0;
   int corrupt_countdown = 0;      // echo_debug_corrupt_tile
+  bool steps_ignore_done = false; // echo_debug_item_steps_ignore_done: one-shot, consumed by the next step-count call that builds its table
   virtual int voice_capture(struct VoiceSnap** out, hipStream_t st) = 0;
   virtual int voice_bind(const struct VoiceSnap* v, hipStream_t st) = 0;
   virtual int dac_decode_tail(const float* lat, int T, int f0, float scale, float* wav, hipStream_t st) = 0;
@@ -217,6 +218,8 @@ struct EngineBase {
                               const int32_t* item_len, int use_latent, const int32_t* ton, const int32_t* son, float* v, hipStream_t st) = 0;
   virtual int sample_euler_items_len(const echo_sampler_params* p, const echo_sampler_item* items, const int32_t* item_pos, const int32_t* item_len,
                                      const float* x0, float* out, hipStream_t st) = 0;
+  virtual int sample_euler_items_steps(const echo_sampler_params* p, const echo_sampler_item* items, const int32_t* item_steps, const int32_t* item_pos,
+                                       const int32_t* item_len, const float* x0, float* out, hipStream_t st) = 0;
 };
 
 // Small host tables go to the device through a ring of pinned staging slots, without a host sync (the pattern of push_nkeys): a
@@ -1658,11 +1661,26 @@ struct Engine : EngineBase {
     if (p && (p->B < 1 || 3 * p->B > MAXROWS)) return fail("per-utterance lengths: at most 32 items per call (3 B <= 96 rows)");
     return sample_euler_items_any(p, items, item_pos, true, x0, out, st, item_len);
   }
+  // Per-utterance step counts: item b runs item_steps[b] <= p->num_steps steps of its own schedule and is left alone afterwards.
+  int sample_euler_items_steps(const echo_sampler_params* p, const echo_sampler_item* items, const int32_t* item_steps, const int32_t* item_pos,
+                               const int32_t* item_len, const float* x0, float* out, hipStream_t st) override {
+    if (!item_steps) return fail("per-utterance step counts: null step-count table");
+    if (fp8) return fail("per-utterance step counts: not supported by the fp8 engine (dit_fp8): the call builds on the length tables, which its e4m3 attention output has no form for; use the bf16 engine");
+    if (p && (p->B < 1 || 3 * p->B > MAXROWS)) return fail("per-utterance step counts: at most 32 items per call (3 B <= 96 rows)");
+    return sample_euler_items_any(p, items, item_pos, item_pos != nullptr || item_len != nullptr, x0, out, st, item_len, item_steps);
+  }
   // with_pos: p->start_pos is ignored, item b starts at item_pos[b] (host, B entries)
   // item_len (host, B entries, with_pos): per-utterance lengths; item_pos may then be null (p->start_pos for every item).  The length forms of
   // the staging and update kernels run instead of the memcpy and euler_items_kernel: x_t of a padding token is 0 from the first launch on.
+  // item_steps (host, B entries): per-utterance step counts.  N = p->num_steps is the call's maximum; item b is ACTIVE in iteration i
+  // while i < item_steps[b] and takes step i of its own table (item_steps[b] entries), FINISHED afterwards.  The distinct counts, in order of first
+  // appearance, are the call's groups (at most MAX_STEP_GROUPS); p->temb is [N][G], entry [i][g] the embedding of group g's i-th timestep (entries
+  // with i >= the group's count are not used; they must be finite).  A forward gets one ModSeg per run of adjacent rows of one group - the caller
+  // orders the items so that groups are contiguous: at most 3 G segments - and a finished item's rows use the modulation of its group's last step, so
+  // that everything they leave in the workspace stays finite.  The *_steps update kernels run instead of euler_items(_len)_kernel.
+  static constexpr int MAX_STEP_GROUPS = 8;
   int sample_euler_items_any(const echo_sampler_params* p, const echo_sampler_item* items, const int32_t* item_pos, bool with_pos, const float* x0,
-                             float* out, hipStream_t st, const int32_t* item_len = nullptr) {
+                             float* out, hipStream_t st, const int32_t* item_len = nullptr, const int32_t* item_steps = nullptr) {
     if (!dit_ready) return fail("echo_finalize_dit was not called");
     if (!p || !items) return fail("mixed sampler call: null params / items");
     const int B = p->B, S = p->S, N = p->num_steps, Lz = cfg.latent_size;
@@ -1670,12 +1688,30 @@ struct Engine : EngineBase {
     if (B < 1 || 3 * B > MAXROWS) return fail("mixed sampler call: at most 32 items per call");
     if (S < 1 || N < 1 || !x0 || !out || !p->temb) return fail("bad sampler params");
     if (spk_T > 0 && (spkB < 1 || kvB % spkB)) return fail("the speaker cache's batch size must divide the text cache's");
+    std::vector<int> grp(B, 0), grp_steps, grp_first;      // item -> group; per group: its step count, its first item
     for (int b = 0; b < B; ++b) {
       if (!items[b].steps) return fail("mixed sampler call: an item has no step table");
+      if (item_steps) {
+        const int n = item_steps[b];
+        if (n < 1) return fail("per-utterance step counts: a step count is below 1");
+        if (n > N) return fail("per-utterance step counts: a step count is above the call's num_steps");
+        int g = 0;
+        while (g < (int)grp_steps.size() && grp_steps[g] != n) ++g;
+        if (g == (int)grp_steps.size()) {
+          if (g == MAX_STEP_GROUPS) return fail("per-utterance step counts: more than 8 distinct step counts in one call");
+          grp_steps.push_back(n); grp_first.push_back(b);
+        }
+        grp[b] = g;
+        for (int i = 0; i < n; ++i)
+          if (items[b].steps[i].dt != items[grp_first[g]].steps[i].dt)
+            return fail("per-utterance step counts: two items of one step count differ in their schedules (dt)");
+        continue;
+      }
       for (int i = 0; i < N; ++i)
         if (items[b].steps[i].dt != items[0].steps[i].dt)
           return fail("mixed sampler call: the items' schedules differ (dt); all items of a call share num_steps and the t schedule");
     }
+    const int G = item_steps ? (int)grp_steps.size() : 1;
     // host side of the step loop, prepared up front: row sets, the (step, item) table, the speaker-KV un-scaling per voice slot
     std::vector<char> any_cfg(N, 0);
     std::vector<EulerItem> tab((size_t)N * B);
@@ -1687,21 +1723,30 @@ struct Engine : EngineBase {
     for (int b = 0; b < B; ++b) init[b] = items[b].has_truncation ? items[b].init_scale : 1.0f;
     for (int i = 0; i < N; ++i) {
       for (int b = 0; b < B; ++b) {
-        const echo_step& sp = items[b].steps[i];
+        // a finished item's entry repeats its last step's and carries `done`: the row set, the CFG window and the KV un-scaling are the active items'
+        const bool active = !item_steps || i < item_steps[b];
+        const echo_step& sp = items[b].steps[active ? i : item_steps[b] - 1];
         EulerItem& t = tab[(size_t)i * B + b];
         t.has_cfg = sp.has_cfg ? 1 : 0; t.s_text = items[b].cfg_scale_text; t.s_spk = items[b].cfg_scale_speaker;
         t.rescale = sp.rescale; t.r_inv1mt = sp.r_inv1mt; t.r_ratio = sp.r_ratio; t.r_1mt = sp.r_1mt; t.dt = sp.dt;
-        if (sp.has_cfg) any_cfg[i] = 1;
+        t.done = active || steps_ignore_done ? 0 : 1;
+        if (sp.has_cfg && active) any_cfg[i] = 1;
         us[b] = 1.0f; ul[b] = items[b].kv_max_layers;
-        if (sp.kv_unscale_after && spk_T > 0) {
+        if (active && sp.kv_unscale_after && spk_T > 0) {
           if (!(items[b].kv_scale != 0.0f) || !std::isfinite(items[b].kv_scale)) return fail("mixed sampler call: kv_scale must be finite and non-zero");
           us[b] = 1.0f / items[b].kv_scale;
           has_unscale[i] = 1;
         }
       }
       memset(&unscale[i], 0, sizeof(KvItemScales));
+      if (has_unscale[i] && item_steps && spkB > 0)      // one slot, one K / V: its items must cross their un-scaling step in the same iteration
+        for (int b = spkB; b < B; ++b)
+          if (item_steps[b] != item_steps[b % spkB] && us[b] != us[b % spkB])
+            return fail("per-utterance step counts: items that share a voice slot and differ in their step counts un-scale its speaker KV at different "
+                        "iterations; the slot's K / V exist once - give each its own voice");
       if (has_unscale[i]) CKI(kv_slot_scales(us.data(), ul.data(), B, unscale[i]));
     }
+    if (item_steps) steps_ignore_done = false;      // the test instrument is one-shot: this call's table has consumed it
     if (item_len) {
       CKI(prepare_item_len(item_pos, item_len, p->start_pos, B, S, st));
       item_pos = len_pos.data();
@@ -1727,7 +1772,7 @@ struct Engine : EngineBase {
     const EulerItem* tab_dev = b_items.as<EulerItem>();
     if (!item_len) CK(hipMemcpyAsync(xs, x0, (size_t)B * S * Lz * sizeof(float), hipMemcpyDeviceToDevice, st));
     else CKI(clear_vt_tail(rows3, S, st));
-    CKI(compute_mod((const T*)p->temb, N, st));
+    CKI(compute_mod((const T*)p->temb, N * G, st));
     if (profiling) CK(hipEventRecord(ev[1], st));
     std::vector<int32_t> ton(rows3, 1), son(rows3, 1);
     for (int b = 0; b < B; ++b) { ton[B + b] = 0; son[2 * B + b] = 0; }
@@ -1741,15 +1786,26 @@ struct Engine : EngineBase {
     e.R_next = any_cfg[0] ? 3 : 1;
     e.init = 1; e.init_scale = (const float*)((const char*)b_items.p + tab_bytes); e.items = tab_dev;
     auto update = [&]() -> hipError_t {
-      if (!item_len) return launch_euler_items<T>(e, st);
+      if (!item_len) return item_steps ? launch_euler_items_steps<T>(e, st) : launch_euler_items<T>(e, st);
       EulerItemsLenArgs el;
       el.a = e; el.len = len_dev(); el.x0 = x0;
-      return launch_euler_items_len<T>(el, st);
+      return item_steps ? launch_euler_items_steps_len<T>(el, st) : launch_euler_items_len<T>(el, st);
     };
     CK(update());
+    std::vector<ModSeg> segs;
     for (int i = 0; i < N; ++i) {
       const int rows = any_cfg[i] ? rows3 : B;
-      CKI(forward_rows(rows, B, S, p->start_pos, p->use_latent != 0, b_mod.as<T>() + (long)i * modstride, st, nullptr, with_pos ? item_pos : nullptr, item_len));
+      if (item_steps) {     // row r takes the table of (its group, its own step i - the last one once it is finished)
+        segs.clear();
+        for (int r = 0; r < rows; ++r) {
+          const int g = grp[r % B];
+          const T* mod = b_mod.as<T>() + ((long)std::min(i, grp_steps[g] - 1) * G + g) * modstride;
+          if (!segs.empty() && segs.back().mod == mod) ++segs.back().nrows;
+          else segs.push_back(ModSeg{r, 1, mod});
+        }
+      }
+      CKI(forward_rows(rows, B, S, p->start_pos, p->use_latent != 0, b_mod.as<T>() + (long)i * modstride, st, item_steps ? &segs : nullptr,
+                       with_pos ? item_pos : nullptr, item_len));
       if (has_unscale[i]) CKI(launch_kv_slot_scales(unscale[i], st));
       e.init = 0;
       e.R = any_cfg[i] ? 3 : 1;
@@ -2816,6 +2872,11 @@ int echo_debug_corrupt_tile(echo_ctx* ctx, int nth) {
   ctx->eng->corrupt_countdown = nth;
   return ECHO_OK;
 }
+int echo_debug_item_steps_ignore_done(echo_ctx* ctx, int on) {
+  if (!ctx) return ECHO_ERR;
+  ctx->eng->steps_ignore_done = on != 0;
+  return ECHO_OK;
+}
 int echo_debug_get_kv(echo_ctx* ctx, int which, int layer, float* k_out, float* v_out, int* B_out, int* T_out) {
   return ctx ? ctx->eng->debug_get_kv(which, layer, k_out, v_out, B_out, T_out) : ECHO_ERR;
 }
@@ -2861,6 +2922,10 @@ int echo_sample_euler_items_len(echo_ctx* ctx, const echo_sampler_params* p, con
 }
 int echo_scale_speaker_kv_items(echo_ctx* ctx, const float* scales_host, const int32_t* max_layers_host, int n, void* stream) {
   return ctx ? ctx->eng->scale_speaker_kv_items(scales_host, max_layers_host, n, (hipStream_t)stream) : ECHO_ERR;
+}
+int echo_sample_euler_items_steps(echo_ctx* ctx, const echo_sampler_params* p, const echo_sampler_item* items, const int32_t* item_steps,
+                                  const int32_t* item_start_pos, const int32_t* item_len, const float* x_init, float* latent_out, void* stream) {
+  return ctx ? ctx->eng->sample_euler_items_steps(p, items, item_steps, item_start_pos, item_len, x_init, latent_out, (hipStream_t)stream) : ECHO_ERR;
 }
 int echo_sample_euler_items(echo_ctx* ctx, const echo_sampler_params* p, const echo_sampler_item* items, const float* x_init, float* latent_out,
                             void* stream) {

@@ -347,7 +347,7 @@ def synthesize(job_input: Dict, model, fish_ae, pca_state, speaker_latent: Optio
 ITEM_PARAM_KEYS = tuple(k for k in SAMPLER_DEFAULTS if k != "sequence_length")      # per utterance; sequence_length and num_steps group calls
 
 
-def plan_mixed_batches(job_inputs: List[Dict], max_batch: int = 24, mix_lengths: bool = False) -> Tuple[List[Dict], List[Dict]]:
+def plan_mixed_batches(job_inputs: List[Dict], max_batch: int = 24, mix_lengths: bool = False, mix_steps: bool = False) -> Tuple[List[Dict], List[Dict]]:
     """Pure planning step of `synthesize_many` (no device work).  Every job is validated as `synthesize` validates it and chunked
     as `_run_job` chunks it; the chunks of all good jobs are grouped by (num_steps, sequence_length) - the two parameters a
     sampler call cannot mix - and cut into calls of at most `max_batch` rows, in job order, chunk order within a job.
@@ -360,7 +360,13 @@ def plan_mixed_batches(job_inputs: List[Dict], max_batch: int = 24, mix_lengths:
 
     `mix_lengths=True`: calls are grouped by num_steps only.  The rows of a group are ordered by sequence_length, longest first (stable:
     job order, chunk order among equals) before they are cut into calls, so that a call's lengths are close; a call then also records
-    "lengths" (one per row) and its "sequence_length" is the longest of them (`inference.sample_euler_items(sequence_length=[...])`)."""
+    "lengths" (one per row) and its "sequence_length" is the longest of them (`inference.sample_euler_items(sequence_length=[...])`).
+
+    `mix_steps=True` (needs `mix_lengths=True`: ValueError otherwise): all rows form ONE group.  They are ordered by (num_steps,
+    sequence_length), both descending (stable), before they are cut into calls; a call then also records "item_steps" (one per row) and
+    its "num_steps" is the largest of them (`inference.sample_euler_items(num_steps=[...])`)."""
+    if mix_steps and not mix_lengths:
+        raise ValueError("mix_steps=True requires mix_lengths=True: a call that mixes step counts also mixes sequence lengths")
     max_batch = max(1, min(int(max_batch), 32))
     jobs: List[Dict] = []
     groups: "OrderedDict[Tuple[int, int], List[Dict]]" = OrderedDict()
@@ -394,18 +400,24 @@ def plan_mixed_batches(job_inputs: List[Dict], max_batch: int = 24, mix_lengths:
                          "normalize_boundaries": parameters.get("normalize_boundaries", True),
                          "enable_crossfade": parameters.get("enable_crossfade", True),
                          "speaker_voice": str(voice) if voice else None, "text_length": len(text)})
-            rows = groups.setdefault((item["num_steps"], -1 if mix_lengths else seq), [])
+            rows = groups.setdefault((-1 if mix_steps else item["num_steps"], -1 if mix_lengths else seq), [])
             for c, piece in enumerate(pieces):
                 rows.append({"job": j, "chunk": c, "text": piece, "seed": seed + c * 1000})
         except Exception as e:
             jobs.append({"error": str(e), "error_type": type(e).__name__, "traceback": traceback.format_exc()})
     calls = []
     for (num_steps, seq), rows in groups.items():
-        if mix_lengths:
+        if mix_steps:
+            rows = sorted(rows, key=lambda r: (-jobs[r["job"]]["item"]["num_steps"], -jobs[r["job"]]["sequence_length"]))
+        elif mix_lengths:
             rows = sorted(rows, key=lambda r: -jobs[r["job"]]["sequence_length"])
         for r0 in range(0, len(rows), max_batch):
             cut = rows[r0:r0 + max_batch]
-            if mix_lengths:
+            if mix_steps:
+                lengths = [jobs[r["job"]]["sequence_length"] for r in cut]
+                item_steps = [jobs[r["job"]]["item"]["num_steps"] for r in cut]
+                calls.append({"num_steps": max(item_steps), "sequence_length": max(lengths), "lengths": lengths, "item_steps": item_steps, "rows": cut})
+            elif mix_lengths:
                 lengths = [jobs[r["job"]]["sequence_length"] for r in cut]
                 calls.append({"num_steps": num_steps, "sequence_length": max(lengths), "lengths": lengths, "rows": cut})
             else:
@@ -417,19 +429,21 @@ _NO_VOICE = "\0no-voice"      # cache key of the one-masked-key voice jobs witho
 
 
 @torch.inference_mode()
-def synthesize_many(job_inputs: List[Dict], model, fish_ae, pca_state, voices=None, max_batch: int = 24, mix_lengths: bool = False) -> List[Dict]:
+def synthesize_many(job_inputs: List[Dict], model, fish_ae, pca_state, voices=None, max_batch: int = 24, mix_lengths: bool = False,
+                    mix_steps: bool = False) -> List[Dict]:
     """Several jobs at once: the text chunks of ALL jobs share sampler calls of up to `max_batch` rows, each row with its own
     request parameters, seed and cached voice (`inference.sample_euler_items`, `EchoDiT.bind_voices`).  Only `num_steps` and
     `sequence_length` cannot be mixed inside a call; jobs are grouped by them (`plan_mixed_batches`).  `mix_lengths=True`: only
     `num_steps` groups; a call runs at its longest row's sequence_length and every shorter row brings its own length
-    (`echo_sample_euler_items_len`; a row's noise and result are those of its own length).
+    (`echo_sample_euler_items_len`; a row's noise and result are those of its own length).  `mix_steps=True` (with `mix_lengths=True`):
+    nothing groups; every row also brings its own `num_steps` (`echo_sample_euler_items_steps`).
 
     `voices`: a `VoiceCache`, or a dict `speaker_voice` name -> (speaker_latent, speaker_mask) or 44.1 kHz audio (1, n); a job
     names its voice with `speaker_voice`, a job without one gets the one-masked-key voice of `sample_pipeline`.  Returns one dict
     per job, in job order: what `synthesize` returns for it, or its own error dict - a bad job does not disturb the others.
     Single-rank: the chunks never enter the data-parallel path of `_run_job`."""
     from .inference import ae_decode, find_flattening_points, get_speaker_latent_and_mask, get_text_input_ids_and_mask, sample_euler_items
-    jobs, calls = plan_mixed_batches(job_inputs, max_batch, mix_lengths=mix_lengths)
+    jobs, calls = plan_mixed_batches(job_inputs, max_batch, mix_lengths=mix_lengths, mix_steps=mix_steps)
     device, dtype, lz = model.device, model.dtype, model.config.latent_size
     cache = voices if isinstance(voices, VoiceCache) else VoiceCache()
     registry = {} if isinstance(voices, VoiceCache) or voices is None else dict(voices)
@@ -465,7 +479,11 @@ def synthesize_many(job_inputs: List[Dict], model, fish_ae, pca_state, voices=No
             handles = [voice_of(jobs[r["job"]]["speaker_voice"]) for r in rows]
             if "lengths" in call:        # rows of failed jobs have left: the lengths of those that stay
                 lengths = [jobs[r["job"]]["sequence_length"] for r in rows]
-                lat = [x.unsqueeze(0) for x in sample_euler_items(model, None, None, ids, tmask, items, sequence_length=lengths, speaker_kv=handles)]
+                steps = [it["num_steps"] for it in items] if "item_steps" in call else None      # the rows that stay bring their own
+                if steps is not None and len(set(steps)) == 1:
+                    steps = None
+                lat = [x.unsqueeze(0) for x in sample_euler_items(model, None, None, ids, tmask, items, sequence_length=lengths, speaker_kv=handles,
+                                                                  num_steps=steps)]
                 cut = [int(find_flattening_points(x)[0]) for x in lat]
             else:
                 lat = sample_euler_items(model, None, None, ids, tmask, items, sequence_length=call["sequence_length"], speaker_kv=handles)

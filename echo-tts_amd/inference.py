@@ -20,7 +20,7 @@ import torch
 
 from . import _lib as L
 from .autoencoder import DAC
-from .model import MAX_ITEMS, EchoDiT, KVHandle, item_lengths, item_start_positions, timestep_embedding
+from .model import MAX_ITEMS, MAX_STEP_GROUPS, EchoDiT, KVHandle, item_lengths, item_start_positions, item_step_counts, timestep_embedding
 
 # --------------------------------------------------------------------------- text front end
 _REPLACEMENTS = (("…", "..."), ("’", "'"), ("”", '"'), ("\n", " "), (":", ","), (";", ","), ("—", ", "))
@@ -324,9 +324,10 @@ _KV_KEYS = ("speaker_kv_scale", "speaker_kv_max_layers", "speaker_kv_min_t")
 _SCHEDULE_KEYS = ("num_steps", "cfg_min_t", "cfg_max_t", "rescale_k", "rescale_sigma", "speaker_kv_scale", "speaker_kv_min_t")
 
 
-def check_sampler_items(items, batch: int, voice_slots: int, need_seed: bool = True) -> None:
+def check_sampler_items(items, batch: int, voice_slots: int, need_seed: bool = True, share_num_steps: bool = True) -> None:
     """Host-side argument checks of `sample_euler_items` (no device work): `batch` text rows, `voice_slots` = batch size of the
-    speaker cache the call will use (item b reads slot b % voice_slots)."""
+    speaker cache the call will use (item b reads slot b % voice_slots).  `share_num_steps=False` (`check_sampler_items_steps`): the
+    items may differ in "num_steps"."""
     items = list(items)
     if len(items) > MAX_ITEMS:
         raise ValueError(f"at most {MAX_ITEMS} items per sampler call (3 rows per item in the CFG layout), got {len(items)}")
@@ -338,7 +339,7 @@ def check_sampler_items(items, batch: int, voice_slots: int, need_seed: bool = T
         if unknown or missing:
             raise ValueError(f"item {b}: unknown keys {sorted(unknown)}, missing keys {sorted(missing)}")
     steps = sorted({int(it["num_steps"]) for it in items})
-    if len(steps) != 1:
+    if share_num_steps and len(steps) != 1:
         raise ValueError(f"all items of one sampler call share num_steps (it sets the t schedule and the launch count); got {steps}")
     if voice_slots < 1 or batch % voice_slots:
         raise ValueError(f"the speaker batch ({voice_slots}) must divide the number of items ({batch})")
@@ -349,15 +350,53 @@ def check_sampler_items(items, batch: int, voice_slots: int, need_seed: bool = T
                              f"{_KV_KEYS}: the slot's K / V exist once")
 
 
-def run_euler_items(model: EchoDiT, x_init: torch.Tensor, item_structs, num_steps: int, temb: torch.Tensor, start_pos=0,
-                    use_latent: bool = False, lengths=None) -> torch.Tensor:
+def check_sampler_items_steps(items, batch: int, voice_slots: int, need_seed: bool = True, num_steps=None, max_steps=None) -> List[int]:
+    """`check_sampler_items` for a call whose items bring their OWN step counts (`sample_euler_items(num_steps=[...])`): everything it checks
+    except "share num_steps".  `num_steps`: None - every item's own "num_steps" key; a list - one count per item (it replaces the key).
+    Returns the B step counts.  ValueError for what the engine refuses: a count below 1, above `max_steps` (the call's maximum; None: the
+    largest count), more than MAX_STEP_GROUPS distinct counts, and two items that share a voice slot, scale its speaker KV and differ in
+    their step counts (their un-scaling steps fall into different iterations, and the slot's K / V exist once).  Pure host code."""
+    items = list(items)
+    check_sampler_items(items, batch, voice_slots, need_seed, share_num_steps=False)
+    counts = item_step_counts([it["num_steps"] for it in items] if num_steps is None else num_steps, batch, max_steps)
+    for b in range(voice_slots, batch):
+        a = b % voice_slots
+        if items[b]["speaker_kv_scale"] is not None and counts[a] != counts[b]:
+            raise ValueError(f"items {a} and {b} share one voice slot, scale its speaker KV (speaker_kv_scale) and run {counts[a]} and {counts[b]} "
+                             f"steps: the scale would be undone at different iterations, and the slot's K / V exist once; give each its own voice")
+    return counts
+
+
+def step_groups_temb(model: EchoDiT, item_steps: Sequence[int], num_steps: int) -> torch.Tensor:
+    """The [N][G] timestep-embedding table of echo_sample_euler_items_steps as an (N * G, timestep_embed) tensor of the model dtype: one
+    column per distinct step count, in order of first appearance, holding the embeddings `build_schedule` makes for a call of that count;
+    past a group's last step its last embedding is repeated (finite, not used for any result)."""
+    cols = []
+    for n in dict.fromkeys(int(v) for v in item_steps):
+        ts = torch.linspace(1.0, 0.0, n + 1) * 0.999                  # inference.py:452,459
+        tv = torch.cat([(torch.ones((1,)) * ts[min(i, n - 1)]).to(model.dtype) for i in range(int(num_steps))])
+        cols.append(timestep_embedding(tv, model.config.timestep_embed_size))
+    return torch.stack(cols, 1).reshape(int(num_steps) * len(cols), -1)
+
+
+def run_euler_items(model: EchoDiT, x_init: torch.Tensor, item_structs, num_steps: int, temb: Optional[torch.Tensor], start_pos=0,
+                    use_latent: bool = False, lengths=None, item_steps=None) -> torch.Tensor:
     """One echo_sample_euler_items call: `item_structs` is a ctypes array of B EchoSamplerItem.  `start_pos`: one int, or a sequence /
     tensor of B ints - every utterance samples its block at its own position (echo_sample_euler_items_pos).  `lengths`: a sequence / tensor
     of B ints, 1 <= n <= S - item b samples lengths[b] latents; `x_init` beyond them is never read and the result is exactly 0 there
-    (echo_sample_euler_items_len)."""
+    (echo_sample_euler_items_len).  `item_steps`: a sequence / tensor of B ints, 1 <= n <= num_steps - item b runs item_steps[b] steps of
+    its own step table and is left alone afterwards (echo_sample_euler_items_steps); `num_steps` is then the call's maximum and `temb` the
+    [N][G] table of `step_groups_temb` (None: built here, one schedule per distinct count).  Items are taken in the order given: put equal
+    step counts next to each other (`sample_euler_items` sorts).  ValueError for what the engine refuses."""
     B, S, _ = x_init.shape
     item_pos = item_start_positions(start_pos, B)
     item_len = item_lengths(lengths, B, S, item_pos if item_pos is not None else start_pos, model.MAX_POS)
+    counts = item_step_counts(item_steps, B, int(num_steps))
+    if counts is not None:
+        if model.fp8:
+            raise ValueError("item_steps: per-utterance step counts are not supported by the fp8 engine")
+        if temb is None:
+            temb = step_groups_temb(model, counts, int(num_steps))
     p = L.EchoSamplerParams()
     p.B, p.S, p.num_steps = B, S, int(num_steps)
     p.start_pos, p.use_latent = (0 if item_pos is not None else int(start_pos or 0)), int(use_latent)
@@ -365,6 +404,12 @@ def run_euler_items(model: EchoDiT, x_init: torch.Tensor, item_structs, num_step
     p.temb = temb_dev.data_ptr()
     x0 = x_init.to(model.device, torch.float32).contiguous()
     out = torch.empty_like(x0)
+    if counts is not None:
+        pos = (C.c_int32 * B)(*item_pos) if item_pos is not None else None
+        ln = (C.c_int32 * B)(*item_len) if item_len is not None else None
+        L.check(model._lib.echo_sample_euler_items_steps(model._ctx, C.byref(p), item_structs, (C.c_int32 * B)(*counts), pos, ln, x0.data_ptr(),
+                                                         out.data_ptr(), model._stream()), model._ctx)
+        return out
     if item_len is not None:
         pos = (C.c_int32 * B)(*item_pos) if item_pos is not None else None       # NULL: p.start_pos for every item
         L.check(model._lib.echo_sample_euler_items_len(model._ctx, C.byref(p), item_structs, pos, (C.c_int32 * B)(*item_len), x0.data_ptr(),
@@ -412,7 +457,7 @@ def _multiply_kv_cache_items(cache: KVHandle, scales, max_layers) -> None:
 
 @torch.inference_mode()
 def sample_euler_items(model: EchoDiT, speaker_latent, speaker_mask, text_input_ids: torch.Tensor, text_mask: torch.Tensor, items, *,
-                       sequence_length=None, x_init: torch.Tensor | None = None, speaker_kv=None):
+                       sequence_length=None, x_init: torch.Tensor | None = None, speaker_kv=None, num_steps=None):
     """reference inference.py:427-517 for B utterances that each bring their OWN request parameters: `items` is a list of B dicts
     with exactly the reference's per-request keys (ITEM_KEYS); row b of the result is what `sample_euler_cfg_independent_guidances`
     computes for row b with items[b].  Per call, not per item: `num_steps` (all items must agree: ValueError).  `sequence_length`: an int
@@ -420,11 +465,23 @@ def sample_euler_items(model: EchoDiT, speaker_latent, speaker_mask, text_input_
     draw it would get alone, the call runs at the longest length with the others padded (`run_euler_items(lengths=)`), and the result is a
     list of (len[b], latent) tensors.  At most 32 items.  `speaker_kv`: one VoiceHandle shared by all rows, or a list of B batch-1 VoiceHandles
     (one cached voice per row, `EchoDiT.bind_voices`); otherwise `speaker_latent` (B or 1 rows) is encoded.  Item b's noise is a
-    (1, S, latent) draw from items[b]["rng_seed"] - the noise the request would get alone - unless `x_init` is given."""
+    (1, S, latent) draw from items[b]["rng_seed"] - the noise the request would get alone - unless `x_init` is given.
+
+    `num_steps`: None - the items' own "num_steps" keys, which must agree (above).  An int - every item runs that many steps (it replaces
+    the keys).  A list of B ints - item b runs num_steps[b] steps of the schedule a call of that step count has, all in ONE call
+    (`run_euler_items(item_steps=)`): the call's rows are sorted by step count, longest first and stable, so that equal
+    counts are adjacent, and the results come back in the caller's order.  A list of equal values gives the bits of the int form.  A speaker
+    cache of batch n with 1 < n < B (rows sharing voice slots) is refused on this path: the sort would move rows to other slots.  Also
+    refused (ValueError): rows that share ONE voice (speaker batch 1), use `speaker_kv_scale` and differ in their step counts - each would
+    undo the scale at another iteration, and the shared K / V exist once; give such rows a voice of their own (`speaker_kv=[...]`)."""
     if sequence_length is None:
         sequence_length = 640
     items = [dict(it) for it in items]
     B = int(text_input_ids.shape[0])
+    if isinstance(num_steps, numbers.Integral):
+        for it in items:
+            it["num_steps"] = int(num_steps)
+        num_steps = None
     lengths = None
     if isinstance(sequence_length, numbers.Integral):
         sequence_length = int(sequence_length)
@@ -438,8 +495,31 @@ def sample_euler_items(model: EchoDiT, speaker_latent, speaker_mask, text_input_
         slots = B
     else:
         slots = int(speaker_kv.batch) if speaker_kv is not None else int(speaker_latent.shape[0])
-    check_sampler_items(items, B, slots, need_seed=x_init is None)
-    device = model.device
+    counts = None
+    if num_steps is None:
+        check_sampler_items(items, B, slots, need_seed=x_init is None)
+    else:
+        # per-item step counts: the call's rows are sorted by step count (longest first, stable); `order[r]` is the caller's row at call row r
+        counts = check_sampler_items_steps(items, B, slots, need_seed=x_init is None, num_steps=num_steps)
+        if slots not in (1, B):
+            raise ValueError(f"num_steps per item: the speaker batch must be 1 (one shared voice) or {B} (one per row), got {slots}")
+        order = sorted(range(B), key=lambda b: -counts[b])
+
+        def take(t):
+            return t[torch.tensor(order, dtype=torch.long, device=t.device)]
+
+        items = [dict(items[b], num_steps=counts[b]) for b in order]
+        counts = [counts[b] for b in order]
+        text_input_ids, text_mask = take(text_input_ids), take(text_mask)
+        if per_row_voices:
+            speaker_kv = [speaker_kv[b] for b in order]
+        elif speaker_kv is None and slots == B:
+            speaker_latent, speaker_mask = take(speaker_latent), take(speaker_mask)
+        if lengths is not None:
+            lengths = [lengths[b] for b in order]
+        if x_init is not None:
+            x_init = take(x_init)
+    device, lz = model.device, model.config.latent_size
     arr, temb, _keep = build_sampler_items(model, items)
     model.get_kv_cache_text(text_input_ids, text_mask)
     if per_row_voices:
@@ -451,7 +531,6 @@ def sample_euler_items(model: EchoDiT, speaker_latent, speaker_mask, text_input_
     if any(it["speaker_kv_scale"] is not None for it in items):
         _multiply_kv_cache_items(kv_spk, [1.0 if it["speaker_kv_scale"] is None else it["speaker_kv_scale"] for it in items],
                                  [it["speaker_kv_max_layers"] for it in items])
-    lz = model.config.latent_size
     if x_init is None and lengths is not None:
         x_init = torch.zeros((B, sequence_length, lz), device=device, dtype=torch.float32)
         for b, it in enumerate(items):
@@ -460,10 +539,14 @@ def sample_euler_items(model: EchoDiT, speaker_latent, speaker_mask, text_input_
     elif x_init is None:
         x_init = torch.cat([torch.randn((1, sequence_length, lz), device=device, dtype=torch.float32,
                                         generator=torch.Generator(device=device).manual_seed(int(it["rng_seed"]))) for it in items], 0)
+    if counts is None:
+        out, rows = run_euler_items(model, x_init, arr, int(items[0]["num_steps"]), temb, lengths=lengths), list(range(B))
+    else:
+        out = run_euler_items(model, x_init, arr, max(counts), None, lengths=lengths, item_steps=counts)
+        rows = [order.index(b) for b in range(B)]                   # call row of the caller's row b
     if lengths is not None:
-        out = run_euler_items(model, x_init, arr, int(items[0]["num_steps"]), temb, lengths=lengths)
-        return [out[b, :lengths[b]] for b in range(B)]
-    return run_euler_items(model, x_init, arr, int(items[0]["num_steps"]), temb)
+        return [out[r, :lengths[r]] for r in rows]
+    return out if counts is None else out[torch.tensor(rows, dtype=torch.long, device=out.device)]
 
 
 # --------------------------------------------------------------------------- pipelines (reference inference.py:308-388)

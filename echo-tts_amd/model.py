@@ -199,6 +199,41 @@ def item_lengths(lengths, batch: int, S: int, start_positions=None, max_pos: Opt
     return out
 
 
+MAX_STEP_GROUPS = 8     # distinct step counts in one sampler call (echo_sample_euler_items_steps: one modulation column per group)
+
+
+def item_step_counts(item_steps, batch: int, num_steps: Optional[int] = None) -> Optional[List[int]]:
+    """None when `item_steps` is None; else the B per-utterance step counts as a list of ints (mirrors `item_lengths`).  ValueError - the
+    engine's refusals, raised before any device work - unless there are exactly `batch` of them, all integers with 1 <= n <= `num_steps`
+    (the call's maximum; None: the largest of them), in at most MAX_STEP_GROUPS distinct values.  Pure host code."""
+    if item_steps is None:
+        return None
+    if isinstance(item_steps, torch.Tensor):
+        if item_steps.dtype.is_floating_point or item_steps.dtype == torch.bool:
+            raise ValueError("item_steps: per-utterance step counts must be integers")
+        vals = item_steps.detach().to("cpu").reshape(-1).tolist()
+    elif isinstance(item_steps, int):
+        raise ValueError(f"item_steps: one step count per item expected ({batch}), got a single int")
+    else:
+        vals = list(item_steps)
+    if len(vals) != batch:
+        raise ValueError(f"item_steps: one step count per item expected ({batch}), got {len(vals)}")
+    out = []
+    for v in vals:
+        if isinstance(v, bool) or int(v) != v:
+            raise ValueError(f"item_steps: per-utterance step counts must be integers, got {v!r}")
+        out.append(int(v))
+    top = max(out) if num_steps is None else int(num_steps)
+    for b, n in enumerate(out):
+        if n < 1:
+            raise ValueError(f"item_steps: a step count is below 1 (item {b}: {n})")
+        if n > top:
+            raise ValueError(f"item_steps: a step count is above the call's num_steps (item {b}: {n} > {top})")
+    if len(set(out)) > MAX_STEP_GROUPS:
+        raise ValueError(f"item_steps: more than {MAX_STEP_GROUPS} distinct step counts in one call ({sorted(set(out))})")
+    return out
+
+
 class EchoDiT:
     """model.py:472 `EchoDiT`, inference only, executed by libechohip."""
 

@@ -18,7 +18,11 @@ Batched decode (`StreamBatcher(batch_decode=True)`): `step_audio()` hands the st
 (`echo_dac_decode_tail_items`: the tails of all streams share the decoder front and every convolution launch) instead of one `push` per
 stream; continuation prefixes are pushed first, in one call of their own.  Off by default (DESIGN.md 3.13 has the measured A/B).
 
-Not here: a captured text KV, incremental prefix encoding, mixed step counts inside one call (streams are grouped by them)."""
+Mixed step counts (`StreamBatcher(mix_block_sizes=True, mix_steps=True)`): a call's key is then empty - streams of any `num_steps` share it,
+each running its own number of steps (`echo_sample_euler_items_steps`); a stream that finishes early rides along to the
+call's last step.  `max_idle_fraction` bounds the share of such idle (stream, step) pairs a call may carry.  Off by default.
+
+Not here: a captured text KV, incremental prefix encoding, dropping a finished stream from a running call."""
 from __future__ import annotations
 
 from dataclasses import dataclass, field
@@ -86,25 +90,40 @@ def padded_share(block_sizes: Sequence[int]) -> float:
     return sum(s_call - int(b) for b in block_sizes) / float(n * s_call)
 
 
-def plan_stream_step_mixed(states: Sequence[StreamState], max_batch: int, max_pad_fraction: Optional[float] = None) -> List[int]:
+def idle_share(step_counts: Sequence[int]) -> float:
+    """sum(N - n_i) / (n * N) of one call, N = the largest step count in it: the share of its (stream, iteration) pairs in which a stream
+    has already finished and only rides along."""
+    n, top = len(step_counts), max(int(v) for v in step_counts)
+    return sum(top - int(v) for v in step_counts) / float(n * top)
+
+
+def plan_stream_step_mixed(states: Sequence[StreamState], max_batch: int, max_pad_fraction: Optional[float] = None, mix_steps: bool = False,
+                           max_idle_fraction: Optional[float] = None) -> List[int]:
     """`plan_stream_step` for calls that mix block sizes: the key of a call is `num_steps` alone.  Pure function of the states.
 
     The leader is chosen as there (longest wait, ties by arrival).  The call is filled in arrival order with open streams of the leader's
     `num_steps`; a candidate is skipped when taking it would raise the call's padded share (`padded_share` of the block sizes taken so far
-    plus its own) above `max_pad_fraction` (None: no limit).  A skipped stream keeps its `waiting_since` and so leads sooner the next time."""
+    plus its own) above `max_pad_fraction` (None: no limit).  A skipped stream keeps its `waiting_since` and so leads sooner the next time.
+
+    `mix_steps=True`: the key of a call is empty - every open stream is a candidate whatever its `num_steps`.  Leader rule and arrival order
+    are unchanged; a candidate is also skipped when taking it would raise the call's idle share (`idle_share` of the step counts taken so far
+    plus its own) above `max_idle_fraction` (None: no limit)."""
     cap = max(1, min(int(max_batch), MAX_ITEMS))
     open_ = [s for s in states if not s.finished]
     if not open_:
         return []
     leader = min(open_, key=lambda s: (s.waiting_since, s.arrival))
-    picked, sizes = [leader.id], [leader.key[0]]
-    for s in sorted((s for s in open_ if s is not leader and int(s.num_steps) == int(leader.num_steps)), key=lambda s: s.arrival):
+    picked, sizes, counts = [leader.id], [leader.key[0]], [int(leader.num_steps)]
+    for s in sorted((s for s in open_ if s is not leader and (mix_steps or int(s.num_steps) == int(leader.num_steps))), key=lambda s: s.arrival):
         if len(picked) >= cap:
             break
         if max_pad_fraction is not None and padded_share(sizes + [s.key[0]]) > float(max_pad_fraction):
             continue
+        if mix_steps and max_idle_fraction is not None and idle_share(counts + [int(s.num_steps)]) > float(max_idle_fraction):
+            continue
         picked.append(s.id)
         sizes.append(s.key[0])
+        counts.append(int(s.num_steps))
     return picked
 
 
@@ -145,11 +164,18 @@ class StreamBatcher:
     `mix_block_sizes=True`: streams whose next blocks differ in size share a call (`plan_stream_step_mixed`, bounded by `max_pad_fraction`);
     the default keeps one call per (block_size, num_steps).
 
-    `batch_decode=True`: `step_audio()` decodes the step's blocks in one `DACStream.push_many` call instead of one `push` per stream."""
+    `batch_decode=True`: `step_audio()` decodes the step's blocks in one `DACStream.push_many` call instead of one `push` per stream.
+
+    `mix_steps=True` (needs `mix_block_sizes=True`: ValueError otherwise): streams with different `num_steps` share a call too, bounded by
+    `max_idle_fraction`; the call's rows are ordered by step count, longest first, and `stats["idle_steps"]` counts the ride-along steps."""
 
     def __init__(self, model, fish_ae, pca_state, voices=None, max_batch: int = 24, mix_block_sizes: bool = False,
-                 max_pad_fraction: Optional[float] = None, batch_decode: bool = False):
+                 max_pad_fraction: Optional[float] = None, batch_decode: bool = False, mix_steps: bool = False,
+                 max_idle_fraction: Optional[float] = None):
         from .handler import VoiceCache
+        if mix_steps and not mix_block_sizes:
+            raise ValueError("mix_steps=True requires mix_block_sizes=True: a call that mixes step counts is planned by plan_stream_step_mixed")
+        self.mix_steps, self.max_idle_fraction = bool(mix_steps), max_idle_fraction
         self.model, self.fish_ae, self.pca_state = model, fish_ae, pca_state
         self.batch_decode = bool(batch_decode)
         self.max_batch = max(1, min(int(max_batch), MAX_ITEMS))
@@ -160,7 +186,8 @@ class StreamBatcher:
         self._next_id = 0
         self._tick = 0
         # ms_*: filled when `timing` is set (adds synchronisation); tokens / pad_tokens: token rows the calls carried / of them padding
-        self.stats = {"calls": 0, "rows": 0, "ms_encode": 0.0, "ms_sample": 0.0, "tokens": 0, "pad_tokens": 0}
+        # steps / idle_steps: (stream, iteration) pairs the calls ran / of them past the stream's own last step
+        self.stats = {"calls": 0, "rows": 0, "ms_encode": 0.0, "ms_sample": 0.0, "tokens": 0, "pad_tokens": 0, "steps": 0, "idle_steps": 0}
         self.timing = False
 
     # ------------------------------------------------------------------ voices
@@ -241,18 +268,26 @@ class StreamBatcher:
 
     @torch.inference_mode()
     def _step(self) -> List[Tuple[int, int, torch.Tensor]]:
-        from .inference import _multiply_kv_cache_items, build_sampler_items, check_sampler_items, run_euler_items
+        from .inference import _multiply_kv_cache_items, build_sampler_items, check_sampler_items, check_sampler_items_steps, run_euler_items
         if self.mix_block_sizes:
-            picked = plan_stream_step_mixed(list(self._streams.values()), self.max_batch, self.max_pad_fraction)
+            picked = plan_stream_step_mixed(list(self._streams.values()), self.max_batch, self.max_pad_fraction, mix_steps=self.mix_steps,
+                                            max_idle_fraction=self.max_idle_fraction)
         else:
             picked = plan_stream_step(list(self._streams.values()), self.max_batch)
         if not picked:
             return []
         m = self.model
         rows = [self._streams[i] for i in picked]
+        if self.mix_steps:       # equal step counts next to each other (one modulation segment per run of rows), longest first, stable
+            rows.sort(key=lambda s: -int(s.num_steps))
         B, ps = len(rows), m.config.speaker_patch_size
         items = [dict(s.item) for s in rows]
-        check_sampler_items(items, B, B, need_seed=False)
+        counts = [int(s.num_steps) for s in rows]
+        mixed_steps = len(set(counts)) > 1           # only with mix_steps
+        if mixed_steps:
+            check_sampler_items_steps(items, B, B, need_seed=False)
+        else:
+            check_sampler_items(items, B, B, need_seed=False)
         arr, temb, _keep = build_sampler_items(m, items)
         if self.timing:
             torch.cuda.synchronize(m.device)
@@ -288,7 +323,10 @@ class StreamBatcher:
             x0 = torch.cat([self._noise(s) for s in rows], 0)
         if self.timing:
             ev[1].record()
-        if mixed:
+        if mixed_steps:
+            x = run_euler_items(m, x0, arr, max(counts), None, start_pos=starts, use_latent=True, lengths=sizes if mixed else None,
+                                item_steps=counts)
+        elif mixed:
             x = run_euler_items(m, x0, arr, rows[0].num_steps, temb, start_pos=starts, use_latent=True, lengths=sizes)
         else:
             x = run_euler_items(m, x0, arr, rows[0].num_steps, temb, start_pos=starts, use_latent=True)
@@ -301,6 +339,8 @@ class StreamBatcher:
         self.stats["rows"] += B
         self.stats["tokens"] += B * max(sizes)
         self.stats["pad_tokens"] += B * max(sizes) - sum(sizes)
+        self.stats["steps"] += B * max(counts)
+        self.stats["idle_steps"] += B * max(counts) - sum(counts)
         self._tick += 1
         out = []
         for b, s in enumerate(rows):
@@ -358,11 +398,13 @@ class StreamBatcher:
 
 
 def stream_audio_many(model, fish_ae, pca_state, requests: Sequence[dict], voices=None, max_batch: int = 24, mix_block_sizes: bool = False,
-                      max_pad_fraction: Optional[float] = None, batch_decode: bool = False) -> Iterator[Tuple[int, torch.Tensor]]:
+                      max_pad_fraction: Optional[float] = None, batch_decode: bool = False, mix_steps: bool = False,
+                      max_idle_fraction: Optional[float] = None) -> Iterator[Tuple[int, torch.Tensor]]:
     """Generator over a list of requests (dicts with the keyword arguments of `StreamBatcher.open`): opens them all and yields
-    `(request index, waveform chunk)` block by block until every stream is done.  `mix_block_sizes` / `max_pad_fraction` / `batch_decode`: `StreamBatcher`."""
+    `(request index, waveform chunk)` block by block until every stream is done.  `mix_block_sizes` / `max_pad_fraction` / `batch_decode` /
+    `mix_steps` / `max_idle_fraction`: `StreamBatcher`."""
     sb = StreamBatcher(model, fish_ae, pca_state, voices=voices, max_batch=max_batch, mix_block_sizes=mix_block_sizes,
-                       max_pad_fraction=max_pad_fraction, batch_decode=batch_decode)
+                       max_pad_fraction=max_pad_fraction, batch_decode=batch_decode, mix_steps=mix_steps, max_idle_fraction=max_idle_fraction)
     index = {sb.open(**dict(r)): i for i, r in enumerate(requests)}
     while sb.open_ids:
         for sid, chunk in sb.step_audio():

@@ -242,6 +242,32 @@ int echo_sample_euler_items_len(echo_ctx* ctx, const echo_sampler_params* p, con
                                 const int32_t* item_start_pos /* host, p->B, may be NULL */, const int32_t* item_len /* host, p->B */,
                                 const float* x_init, float* latent_out, void* stream);
 
+/* ---- per-utterance step counts (additive: every declaration above keeps its layout, its bits and its refusals; ECHO_ABI_VERSION stays 8) ----
+ * One sampler call for utterances that run DIFFERENT numbers of Euler steps (a 20-step "fast" request next to a 40-step one).
+ *   - item_steps: HOST table of B int32, 1 <= item_steps[b] <= p->num_steps.  p->num_steps = N is the call's maximum: the call runs N iterations.
+ *   - items[b].steps has item_steps[b] entries: the item's OWN schedule, what a uniform call of that step count would be given.
+ *   - the distinct step counts, in order of first appearance in item_steps, are the call's G groups (G <= 8).  p->temb is a table [N][G] of timestep
+ *     embeddings (row i * G + g, timestep_embed wide): entry [i][g] belongs to step i of group g's schedule.  Entries with i >= the group's count are
+ *     not used for any result; they must be finite (the host repeats the group's last one).  With G = 1 this is the (num_steps, timestep_embed)
+ *     table of the calls above.
+ *   - iteration i: item b is ACTIVE while i < item_steps[b] and takes its own step i (CFG window, rescale, dt, speaker-KV un-scaling at its own
+ *     step); afterwards it is FINISHED: its x_t is not written again, so latent_out holds the bits it had after its last step.
+ *   - the row set of an iteration (3 B rows with CFG, B without) is decided by the ACTIVE items' CFG windows alone.
+ *   - the layout stays rectangular: a finished item's rows are still computed (with the modulation of its last step, so every workspace value
+ *     stays finite) and nobody reads them - the stated cost, like padding tokens and CFG ride-along rows.  Each group adds one launch of the four
+ *     modulation-reading kernels per block and row run: ORDER THE ITEMS SO THAT EQUAL STEP COUNTS ARE ADJACENT (at most 3 G row runs; the host
+ *     layer sorts by step count).  Any order is computed correctly.
+ *   - item_start_pos / item_len may each be NULL and mean what they mean in echo_sample_euler_items_len; both NULL: every item at p->start_pos with
+ *     all S tokens (the layout of echo_sample_euler_items).
+ *   - all counts equal to N: the bits of echo_sample_euler_items / _pos / _len for the same tables.
+ * Fails (non-zero, echo_last_error; nothing is queued, latent_out is not written, the context stays usable) on a NULL item_steps, a count below 1 or
+ * above p->num_steps, two items of one step count whose steps[i].dt differ, more than 8 distinct counts, a context created with dit_fp8, items
+ * that share a voice slot (speaker cache of batch spkB < B, slot b % spkB), differ in their step counts and un-scale their speaker KV (their
+ * kv_unscale_after steps fall into different iterations; the slot's K / V exist once), and on everything the calls it extends fail on. */
+int echo_sample_euler_items_steps(echo_ctx* ctx, const echo_sampler_params* p, const echo_sampler_item* items /* p->B entries */,
+                                  const int32_t* item_steps /* host, p->B */, const int32_t* item_start_pos /* host, p->B, may be NULL */,
+                                  const int32_t* item_len /* host, p->B, may be NULL */, const float* x_init, float* latent_out, void* stream);
+
 /* inference.py:226-229 ae_decode -> autoencoder.py:1128-1132 DAC.decode_zq, one batch item:
  * latent (T, latent_size) fp32 -> wav (T * hop) fp32.
  * ECHO_BF16 context (ABI 8): the PCA inverse is evaluated in fp32 and rounded to bf16 once (inference.py:227-229), the decoder runs in bf16 and the
@@ -406,6 +432,11 @@ int echo_debug_get_kv(echo_ctx* ctx, int which, int layer, float* k_out, float* 
  * columns 256..511) negated right after the launch - what one wrong entry in a kernel's tile walk would produce.  nth = 0 disarms.
  * tests/test_gpu_engine.py shows that its full-depth checks reject such a forward. */
 int echo_debug_corrupt_tile(echo_ctx* ctx, int nth);
+/* test instrument of the same kind for echo_sample_euler_items_steps, ONE-SHOT like the countdown above: on != 0 -> the NEXT accepted call builds
+ * its (step, item) table WITHOUT the `done` flag, so a finished item is updated again with its last step's entry - what an update kernel that
+ * ignored the flag would do - and disarms the instrument; every later call is a normal one.  0 disarms at once.
+ * tests/test_gpu_item_steps.py shows that its frozen-item check rejects such a call. */
+int echo_debug_item_steps_ignore_done(echo_ctx* ctx, int on);
 
 /* timing of the engine's phases, filled by the last echo_sample_euler / echo_dac_decode when
  * echo_set_profiling(ctx, 1) was called (HIP events on the caller's stream; adds synchronisation) */
