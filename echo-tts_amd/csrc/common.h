@@ -210,8 +210,9 @@ template <typename T>
 hipError_t launch_headnorm_rope_nt(T* x, long ldx, long t_stride, int nt, int rows, int S, int H, const T* w, long w_stride,
                                    float eps, int do_norm, int rope_heads, const float2* rope, int pos0, int pos_mul,
                                    hipStream_t st);
-// out[b * S + s] = rope[start[b] + s] (rows of 64 float2): the per-call RoPE table of a forward with one start position per utterance
-hipError_t launch_rope_gather(const float2* rope, const int* start_dev, float2* out, int B, int S, hipStream_t st);
+// out[b * S + s] = rope[start[b] + min(s, len[b] - 1)] (rows of 64 float2): the per-call RoPE table of a forward with one start position and one
+// length per utterance (device tables, B entries; len[b] = S: every token its own row).  start[b] + len[b] bounds the reads.
+hipError_t launch_rope_gather(const float2* rope, const int* start_dev, const int* len_dev, float2* out, int B, int S, hipStream_t st);
 template <typename T> hipError_t launch_embedding(const int* ids, const T* table, T* out, long ldo, int n, int D, hipStream_t st);
 template <typename T> hipError_t launch_silu(const T* x, T* y, long n, hipStream_t st);
 // bf16 rows -> OCP e4m3 bytes + per-row fp32 scale (amax / 448)
@@ -253,37 +254,27 @@ struct EulerItem {
   int has_cfg; float s_text, s_spk;
   int rescale; float r_inv1mt, r_ratio, r_1mt;
   float dt;
-  int done;                 // per-utterance step counts: the item finished at an earlier iteration; read by the *_steps kernels only
+  int done;                 // per-utterance step counts: the item finished at an earlier iteration (0 in a call without step counts)
 };
+// One launch of the mixed sampler's update.  init: x = x0 * init_scale for valid tokens (the table entry is not read).  step: the Euler update
+// of an item's valid tokens; an item with done != 0 keeps x as it is (no store to x at all) and only has the next forward's input staged
+// from it.  Token s of item b is padding when s >= len[b]: never read from x0, written as 0 by the init launch, 0 ever after.
 struct EulerItemsArgs {
   float* x; const void* v; long ldv; void* xin; long ld_xin;      // as EulerArgs
   int B, S, L, R, R_next;
   const EulerItem* items;   // device, B entries: this step's (unused by the init launch)
   const float* init_scale;  // device, B floats (1.0f = no truncation); read by the init launch only
+  const int* len;           // device, B entries, 1 <= len[b] <= S; nullptr: every token is valid
+  const float* x0;          // the caller's x_init (B, S, L): read by the init launch, valid tokens only
   int init;
 };
 template <typename T> hipError_t launch_euler_items(const EulerItemsArgs& e, hipStream_t st);
 
-// Per-utterance lengths: token s of item b is padding when s >= len[b] (device table, B entries).  The length forms of the
-// sampler update and of the two staging copies never read a padding token of the caller's tensors and write zeros for it.
-struct EulerItemsLenArgs {
-  EulerItemsArgs a;
-  const int* len;           // device, B entries, 1 <= len[b] <= S
-  const float* x0;          // the caller's x_init (B, S, L): read by the init launch, valid tokens only
-};
-// init: x = x0 * init_scale for valid tokens, 0 for padding.  step: euler_items_kernel's arithmetic for valid tokens; padding keeps x = 0.
-template <typename T> hipError_t launch_euler_items_len(const EulerItemsLenArgs& e, hipStream_t st);
-// Per-utterance step counts: the two launches above for a table whose entries carry `done`.  An item with done == 0 gets
-// their arithmetic, operation for operation; an item with done != 0 keeps x as it is (no store to x at all) and only has the next
-// forward's input staged from it.  The init launch is theirs.
-template <typename T> hipError_t launch_euler_items_steps(const EulerItemsArgs& e, hipStream_t st);
-template <typename T> hipError_t launch_euler_items_steps_len(const EulerItemsLenArgs& e, hipStream_t st);
+// The length forms of the two staging copies never read a padding token of the caller's tensors and write zeros for it.
 // xin[(r * S + s)][l < L] = s < len[r % B] ? x[(r * S + s)][l] : 0   (x, xin of T; the columns L.. of xin stay as they are: zero)
 template <typename T> hipError_t launch_stage_x_len(const T* x, int L, T* xin, long ld_xin, int rows, int B, int S, const int* len, hipStream_t st);
 // y[(r * S + s)][l < cols] = s < len[r % B] ? float(x[(r * S + s)][l]) : 0
 template <typename T> hipError_t launch_convert_to_f32_len(const T* x, long ldx, float* y, long ldy, int rows, int B, int S, int cols, const int* len, hipStream_t st);
-// launch_rope_gather for items shorter than S: out[b * S + s] = rope[start[b] + min(s, len[b] - 1)], so that start[b] + len[b] bounds the reads
-hipError_t launch_rope_gather_len(const float2* rope, const int* start_dev, const int* len_dev, float2* out, int B, int S, hipStream_t st);
 
 // Per-item speaker-KV scaling: item b's K | V rows and its V^T rows of layers < nl[b] are multiplied by s[b] (rounding of
 // launch_scale_2d); an item with s == 1 or nl == 0 is not touched.  kv: (nB * Tn, ld) with layer l at columns [l * 2D, (l + 1) * 2D);

@@ -313,11 +313,9 @@ __global__ void euler_kernel(const EulerArgs e) {
   for (int r = 0; r < e.R_next; ++r) xin[(r * bs + tok) * e.ld_xin + l] = Num<T>::st(x);
 }
 
-// One token element of a mixed call's Euler step (CFG combine, temporal rescale, update): the ONE statement of that arithmetic, shared by
-// euler_items_kernel and its length form.
+// One token element of a mixed call's Euler step (CFG combine, temporal rescale, update): the ONE statement of that arithmetic.
 template <typename T>
-__device__ __forceinline__ float euler_item_update(const EulerItemsArgs& e, const int item, const long tok, const int l, const long bs, float x) {
-  const EulerItem it = e.items[item];
+__device__ __forceinline__ float euler_item_update(const EulerItemsArgs& e, const EulerItem& it, const long tok, const int l, const long bs, float x) {
   const T* v = (const T*)e.v;
   float vp = Num<T>::ld(v[tok * e.ldv + l]);
   if (e.R == 3 && it.has_cfg) {
@@ -336,9 +334,15 @@ __device__ __forceinline__ float euler_item_update(const EulerItemsArgs& e, cons
   return x;
 }
 
-// The same update with per-utterance parameters (echo_sample_euler_items): item = tok / S reads its own table entry.  The arithmetic is
-// euler_kernel's, operation for operation, so an item whose entry equals a uniform call's launch scalars gets the same bits.  R == 3
-// means "some item has CFG at this step"; an item without it takes v_cond as it is (its two un-conditional rows ride along unused).
+// euler_kernel with per-utterance parameters (echo_sample_euler_items and its _pos / _len / _steps forms): item = tok / S reads its own table
+// entry.  The arithmetic is euler_kernel's, operation for operation, so an item whose entry equals a uniform call's launch scalars gets the
+// same bits.  R == 3 means "some item has CFG at this step"; an item without it takes v_cond as it is (its two un-conditional rows ride along
+// unused).
+//   - A padding token (e.len and s >= len[item]) is never read from the caller's x_init, is written as 0 by the init launch and
+//     stays 0: its update is skipped.
+//   - An item whose entry carries `done` (the iteration is past its last step) has its x loaded only to stage the next
+//     forward's input (the layout stays rectangular, its rows are computed and nobody reads them) and NOT stored: x_t keeps the bits of the
+//     item's last step.
 template <typename T>
 __global__ void euler_items_kernel(const EulerItemsArgs e) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -348,96 +352,25 @@ __global__ void euler_items_kernel(const EulerItemsArgs e) {
   const int l = (int)(i - tok * e.L);
   const int item = (int)(tok / e.S);
   const long bs = (long)e.B * e.S;
-  float x = e.x[i];
-  if (e.init) {
-    const float s = e.init_scale[item];
-    if (s != 1.0f) x = __fmul_rn(x, s);
-  } else {
-    x = euler_item_update<T>(e, item, tok, l, bs, x);
-  }
-  e.x[i] = x;
-  T* xin = (T*)e.xin;
-  for (int r = 0; r < e.R_next; ++r) xin[(r * bs + tok) * e.ld_xin + l] = Num<T>::st(x);
-}
-
-// Per-utterance lengths.  The update of a valid token is euler_items_kernel's, operation for operation; a padding token
-// (s >= len[item]) is never read from the caller's x_init, is written as 0 by the init launch and stays 0: its update is skipped.
-template <typename T>
-__global__ void euler_items_len_kernel(const EulerItemsLenArgs p) {
-  const EulerItemsArgs& e = p.a;
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  const long n = (long)e.B * e.S * e.L;
-  if (i >= n) return;
-  const long tok = i / e.L;
-  const int l = (int)(i - tok * e.L);
-  const int item = (int)(tok / e.S);
-  const long bs = (long)e.B * e.S;
-  const bool valid = (int)(tok - (long)item * e.S) < p.len[item];
+  const bool valid = !e.len || (int)(tok - (long)item * e.S) < e.len[item];
   float x = 0.0f;
-  if (valid) {
-    if (e.init) {
-      x = p.x0[i];
+  bool store = true;
+  if (e.init) {
+    if (valid) {
+      x = e.x0[i];
       const float s = e.init_scale[item];
       if (s != 1.0f) x = __fmul_rn(x, s);
-    } else {
-      x = euler_item_update<T>(e, item, tok, l, bs, e.x[i]);
     }
-  }
-  e.x[i] = x;
-  T* xin = (T*)e.xin;
-  for (int r = 0; r < e.R_next; ++r) xin[(r * bs + tok) * e.ld_xin + l] = Num<T>::st(x);
-}
-// Per-utterance step counts: iteration i of the call is past the last step of an item whose entry carries `done`.  Such an
-// item's x is loaded only to stage the next forward's input (the layout stays rectangular, its rows are computed and nobody reads them) and
-// is NOT stored: x_t keeps the bits of the item's last step.  Every other item takes euler_items_kernel's path, operation for operation.
-template <typename T>
-__global__ void euler_items_steps_kernel(const EulerItemsArgs e) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  const long n = (long)e.B * e.S * e.L;
-  if (i >= n) return;
-  const long tok = i / e.L;
-  const int l = (int)(i - tok * e.L);
-  const int item = (int)(tok / e.S);
-  const long bs = (long)e.B * e.S;
-  float x = e.x[i];
-  if (e.init) {
-    const float s = e.init_scale[item];
-    if (s != 1.0f) x = __fmul_rn(x, s);
-    e.x[i] = x;
-  } else if (!e.items[item].done) {
-    x = euler_item_update<T>(e, item, tok, l, bs, x);
-    e.x[i] = x;
-  }
-  T* xin = (T*)e.xin;
-  for (int r = 0; r < e.R_next; ++r) xin[(r * bs + tok) * e.ld_xin + l] = Num<T>::st(x);
-}
-// The length form: euler_items_len_kernel for an item that still runs; a finished item's x (0 at its padding since the init launch) is staged, not stored.
-template <typename T>
-__global__ void euler_items_steps_len_kernel(const EulerItemsLenArgs p) {
-  const EulerItemsArgs& e = p.a;
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  const long n = (long)e.B * e.S * e.L;
-  if (i >= n) return;
-  const long tok = i / e.L;
-  const int l = (int)(i - tok * e.L);
-  const int item = (int)(tok / e.S);
-  const long bs = (long)e.B * e.S;
-  float x;
-  if (!e.init && e.items[item].done) {
-    x = e.x[i];
   } else {
-    x = 0.0f;
-    if ((int)(tok - (long)item * e.S) < p.len[item]) {
-      if (e.init) {
-        x = p.x0[i];
-        const float s = e.init_scale[item];
-        if (s != 1.0f) x = __fmul_rn(x, s);
-      } else {
-        x = euler_item_update<T>(e, item, tok, l, bs, e.x[i]);
-      }
+    const EulerItem it = e.items[item];
+    if (it.done) {
+      x = e.x[i];
+      store = false;
+    } else if (valid) {
+      x = euler_item_update<T>(e, it, tok, l, bs, e.x[i]);
     }
-    e.x[i] = x;
   }
+  if (store) e.x[i] = x;
   T* xin = (T*)e.xin;
   for (int r = 0; r < e.R_next; ++r) xin[(r * bs + tok) * e.ld_xin + l] = Num<T>::st(x);
 }
@@ -862,25 +795,8 @@ template <typename T> hipError_t launch_euler(const EulerArgs& e, hipStream_t st
   return hipGetLastError();
 }
 template <typename T> hipError_t launch_euler_items(const EulerItemsArgs& e, hipStream_t st) {
-  if (!e.x || !e.xin || (e.init ? !e.init_scale : (!e.items || !e.v)) || e.B < 1 || e.S < 1 || e.L < 1) return hipErrorInvalidValue;
+  if (!e.x || !e.xin || (e.init ? (!e.init_scale || !e.x0) : (!e.items || !e.v)) || e.B < 1 || e.S < 1 || e.L < 1) return hipErrorInvalidValue;
   hipLaunchKernelGGL(euler_items_kernel<T>, grid1d((long)e.B * e.S * e.L), dim3(256), 0, st, e);
-  return hipGetLastError();
-}
-template <typename T> hipError_t launch_euler_items_len(const EulerItemsLenArgs& p, hipStream_t st) {
-  const EulerItemsArgs& e = p.a;
-  if (!e.x || !e.xin || !p.len || (e.init ? (!e.init_scale || !p.x0) : (!e.items || !e.v)) || e.B < 1 || e.S < 1 || e.L < 1) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(euler_items_len_kernel<T>, grid1d((long)e.B * e.S * e.L), dim3(256), 0, st, p);
-  return hipGetLastError();
-}
-template <typename T> hipError_t launch_euler_items_steps(const EulerItemsArgs& e, hipStream_t st) {
-  if (!e.x || !e.xin || (e.init ? !e.init_scale : (!e.items || !e.v)) || e.B < 1 || e.S < 1 || e.L < 1) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(euler_items_steps_kernel<T>, grid1d((long)e.B * e.S * e.L), dim3(256), 0, st, e);
-  return hipGetLastError();
-}
-template <typename T> hipError_t launch_euler_items_steps_len(const EulerItemsLenArgs& p, hipStream_t st) {
-  const EulerItemsArgs& e = p.a;
-  if (!e.x || !e.xin || !p.len || (e.init ? (!e.init_scale || !p.x0) : (!e.items || !e.v)) || e.B < 1 || e.S < 1 || e.L < 1) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(euler_items_steps_len_kernel<T>, grid1d((long)e.B * e.S * e.L), dim3(256), 0, st, p);
   return hipGetLastError();
 }
 template <typename T>
@@ -969,29 +885,13 @@ hipError_t launch_quant_rows_fp8(const void* x, long ldx, void* q, long ldq, flo
                      rows, K);
   return hipGetLastError();
 }
-// Per-utterance start positions: out[b * S + s] = rope[start[b] + s], one 512-byte row of 64 (cos, sin) pairs per token,
-// copied as 32 x 16 bytes.  The RoPE consumers then address the copy as m % (B * S) (GemmArgs.rope_mod) and read the very values a call
-// with the launch scalar start[b] reads.  The caller has checked 0 <= start[b] and start[b] + S <= rows of `rope`.
-__global__ void __launch_bounds__(256) rope_gather_kernel(const float4* __restrict__ rope, const int* __restrict__ start, float4* __restrict__ out,
-                                                          int B, int S) {
-  const long n = (long)B * S * 32;
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
-    const int row = (int)(i >> 5), j = (int)(i & 31);
-    const int b = row / S, s = row - b * S;
-    out[i] = rope[(long)(start[b] + s) * 32 + j];
-  }
-}
-hipError_t launch_rope_gather(const float2* rope, const int* start_dev, float2* out, int B, int S, hipStream_t st) {
-  if (!rope || !start_dev || !out || B < 1 || S < 1 || ((uintptr_t)rope & 15) || ((uintptr_t)out & 15)) return hipErrorInvalidValue;
-  const long vectors = (long)B * S * 32;
-  hipLaunchKernelGGL(rope_gather_kernel, dim3((unsigned)std::max(1L, std::min((vectors + 255) / 256, 2048L))), dim3(256), 0, st, (const float4*)rope,
-                     start_dev, (float4*)out, B, S);
-  return hipGetLastError();
-}
-// rope_gather_kernel for items shorter than the call: a padding token takes the row of its item's last valid position, so
-// that the reads stay below start[b] + len[b] (what the caller has checked against the table) and every padding q / k stays finite.
-__global__ void __launch_bounds__(256) rope_gather_len_kernel(const float4* __restrict__ rope, const int* __restrict__ start, const int* __restrict__ len,
-                                                              float4* __restrict__ out, int B, int S) {
+// Per-utterance start positions and lengths: out[b * S + s] = rope[start[b] + min(s, len[b] - 1)], one 512-byte row of
+// 64 (cos, sin) pairs per token, copied as 32 x 16 bytes.  The RoPE consumers then address the copy as m % (B * S) (GemmArgs.rope_mod) and
+// read the very values a call with the launch scalar start[b] reads.  A padding token (s >= len[b]) takes the row of its item's last valid
+// position, so that the reads stay below start[b] + len[b] and every padding q / k stays finite; len[b] = S: every token its own row.
+// The caller has checked 0 <= start[b], 1 <= len[b] <= S and start[b] + len[b] <= rows of `rope`.
+__global__ void __launch_bounds__(256) rope_gather_kernel(const float4* __restrict__ rope, const int* __restrict__ start, const int* __restrict__ len,
+                                                          float4* __restrict__ out, int B, int S) {
   const long n = (long)B * S * 32;
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
     const int row = (int)(i >> 5), j = (int)(i & 31);
@@ -999,10 +899,10 @@ __global__ void __launch_bounds__(256) rope_gather_len_kernel(const float4* __re
     out[i] = rope[(long)(start[b] + min(s, len[b] - 1)) * 32 + j];
   }
 }
-hipError_t launch_rope_gather_len(const float2* rope, const int* start_dev, const int* len_dev, float2* out, int B, int S, hipStream_t st) {
+hipError_t launch_rope_gather(const float2* rope, const int* start_dev, const int* len_dev, float2* out, int B, int S, hipStream_t st) {
   if (!rope || !start_dev || !len_dev || !out || B < 1 || S < 1 || ((uintptr_t)rope & 15) || ((uintptr_t)out & 15)) return hipErrorInvalidValue;
   const long vectors = (long)B * S * 32;
-  hipLaunchKernelGGL(rope_gather_len_kernel, dim3((unsigned)std::max(1L, std::min((vectors + 255) / 256, 2048L))), dim3(256), 0, st, (const float4*)rope,
+  hipLaunchKernelGGL(rope_gather_kernel, dim3((unsigned)std::max(1L, std::min((vectors + 255) / 256, 2048L))), dim3(256), 0, st, (const float4*)rope,
                      start_dev, len_dev, (float4*)out, B, S);
   return hipGetLastError();
 }
@@ -1027,9 +927,6 @@ hipError_t launch_mask_to_bias(const uint8_t* mask, float* bias, long n, hipStre
   template hipError_t launch_convert_to_f32<T>(const T*, long, float*, long, int, int, hipStream_t);                         \
   template hipError_t launch_euler<T>(const EulerArgs&, hipStream_t);                                                        \
   template hipError_t launch_euler_items<T>(const EulerItemsArgs&, hipStream_t);                                             \
-  template hipError_t launch_euler_items_len<T>(const EulerItemsLenArgs&, hipStream_t);                                      \
-  template hipError_t launch_euler_items_steps<T>(const EulerItemsArgs&, hipStream_t);                                       \
-  template hipError_t launch_euler_items_steps_len<T>(const EulerItemsLenArgs&, hipStream_t);                                \
   template hipError_t launch_stage_x_len<T>(const T*, int, T*, long, int, int, int, const int*, hipStream_t);                \
   template hipError_t launch_convert_to_f32_len<T>(const T*, long, float*, long, int, int, int, int, const int*, hipStream_t); \
   template hipError_t launch_scale_kv_items<T>(T*, long, T*, long, int, int, int, const KvItemScales&, hipStream_t);         \

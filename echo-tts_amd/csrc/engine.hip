@@ -182,8 +182,10 @@ struct EngineBase {
   virtual int encode_speaker(const void* lat, const float* bias, const int32_t* nk, int B, int Ts, hipStream_t st) = 0;
   virtual int encode_latent(const void* lat, int B, int n, long row_stride, hipStream_t st) = 0;
   virtual int scale_speaker_kv(float s, int max_layers, hipStream_t st) = 0;
-  virtual int dit_forward(const void* x, const void* temb, int n_t, const int32_t* row_t, int rows, int B, int S, int start_pos, int use_latent,
-                          const int32_t* ton, const int32_t* son, float* v, hipStream_t st) = 0;
+  // item_pos / item_len (host tables of B entries, each may be null): per-utterance start positions (start_pos is then ignored) / lengths
+  virtual int dit_forward(const void* x, const void* temb, int n_t, const int32_t* row_t, int rows, int B, int S, int start_pos,
+                          const int32_t* item_pos, const int32_t* item_len, int use_latent, const int32_t* ton, const int32_t* son, float* v,
+                          hipStream_t st) = 0;
   virtual int sample_euler(const echo_sampler_params* p, const float* x0, float* out, hipStream_t st) = 0;
   virtual int dac_decode(const float* lat, int T, float scale, float* wav, hipStream_t st) = 0;
   virtual int dac_decode_zq(const float* z, int T, float* wav, hipStream_t st) = 0;
@@ -194,6 +196,7 @@ struct EngineBase {
   virtual int set_pca_encode(const float* w, const float* bias, float scale, int on_device, hipStream_t st) = 0;
   virtual int debug_get_kv(int which, int layer, float* k, float* v, int* B, int* T) = 0;
   int corrupt_countdown = 0;      // echo_debug_corrupt_tile
+  bool fp8 = false;               // bf16 engine with cfg.dit_fp8, set by finalize_dit (the step-count entry point refuses it in its own words)
   bool steps_ignore_done = false; // echo_debug_item_steps_ignore_done: one-shot, consumed by the next step-count call that builds its table
   virtual int voice_capture(struct VoiceSnap** out, hipStream_t st) = 0;
   virtual int voice_bind(const struct VoiceSnap* v, hipStream_t st) = 0;
@@ -205,21 +208,11 @@ struct EngineBase {
   virtual int fp8_calibration(float* out, int n) = 0;
   virtual int fp8_set_static(const float* s, int n) = 0;
   // mixed batches (added under ABI 8): per-utterance sampler parameters, speaker-KV scaling and cached voices in one call
-  virtual int sample_euler_items(const echo_sampler_params* p, const echo_sampler_item* items, const float* x0, float* out, hipStream_t st) = 0;
+  // item_pos / item_len / item_steps (host tables of B entries, each may be null): per-utterance start positions / lengths / step counts
+  virtual int sample_euler_items(const echo_sampler_params* p, const echo_sampler_item* items, const int32_t* item_pos, const int32_t* item_len,
+                                 const int32_t* item_steps, const float* x0, float* out, hipStream_t st) = 0;
   virtual int scale_speaker_kv_items(const float* scales, const int32_t* max_layers, int n, hipStream_t st) = 0;
   virtual int voice_bind_items(const struct VoiceSnap* const* v, int n, hipStream_t st) = 0;
-  // per-utterance start positions (staggered streaming batches): item_pos is a host table of B entries
-  virtual int dit_forward_pos(const void* x, const void* temb, int n_t, const int32_t* row_t, int rows, int B, int S, const int32_t* item_pos,
-                              int use_latent, const int32_t* ton, const int32_t* son, float* v, hipStream_t st) = 0;
-  virtual int sample_euler_items_pos(const echo_sampler_params* p, const echo_sampler_item* items, const int32_t* item_pos, const float* x0,
-                                     float* out, hipStream_t st) = 0;
-  // per-utterance lengths (calls that mix block sizes / sequence lengths): item_len is a host table of B entries, item_pos may be null
-  virtual int dit_forward_len(const void* x, const void* temb, int n_t, const int32_t* row_t, int rows, int B, int S, const int32_t* item_pos,
-                              const int32_t* item_len, int use_latent, const int32_t* ton, const int32_t* son, float* v, hipStream_t st) = 0;
-  virtual int sample_euler_items_len(const echo_sampler_params* p, const echo_sampler_item* items, const int32_t* item_pos, const int32_t* item_len,
-                                     const float* x0, float* out, hipStream_t st) = 0;
-  virtual int sample_euler_items_steps(const echo_sampler_params* p, const echo_sampler_item* items, const int32_t* item_steps, const int32_t* item_pos,
-                                       const int32_t* item_len, const float* x0, float* out, hipStream_t st) = 0;
 };
 
 // Small host tables go to the device through a ring of pinned staging slots, without a host sync (the pattern of push_nkeys): a
@@ -310,8 +303,9 @@ struct Engine : EngineBase {
   static constexpr size_t POS_TAB_BYTES = 512;
   static constexpr int LEN_TAB_OFF = 64;      // per-utterance lengths: int32 entries [LEN_TAB_OFF, LEN_TAB_OFF + B) of the same table, sent in the same copy
   const int* len_dev() const { return b_pos_rope.as<int>() + LEN_TAB_OFF; }
-  std::vector<int32_t> len_pos;     // the start positions of the running length call (a null position table resolved)
-  const int* attn_qlen = nullptr;   // set by forward_rows around the joint attention of a length call: AttnArgs.qlen
+  // The per-utterance host tables of one forward / sampler call as prepare_item_tables() resolved them: both null (every item at the call's
+  // start_pos with S tokens), or pos alone, or both.
+  struct ItemTables { const int32_t* pos = nullptr; const int32_t* len = nullptr; };
   HostStage stage_items;
   std::vector<DevBuf*> all_bufs() {
     return {&b_kv_text, &b_vt_text, &b_kv_spk, &b_vt_spk, &b_kv_lat, &b_vt_lat, &b_nkeys, &b_bias_text, &b_bias_spk,
@@ -377,7 +371,6 @@ struct Engine : EngineBase {
   int device_key() { int d = 0; (void)hipGetDevice(&d); return d; }
   DevBuf b_gemm_ws, b_tune_c, b_flush;
   // ------------------------------------------------------------------ fp8 operands (config dit_fp8, bf16 engine; BASELINE C5)
-  bool fp8 = false;
   std::vector<uint8_t*> q_wqkvg, q_wo, q_w13, q_w2;     // e4m3 copies of the packed block weights
   std::vector<float*> s_wqkvg, s_wo, s_w13, s_w2;       // one scale per weight row
   DevBuf b_q8, b_qs;                                    // quantised A operand of the current GEMM + its row scales
@@ -711,7 +704,8 @@ struct Engine : EngineBase {
   };
   // q/gate/out live in [rows*S][..] buffers with per-row stride S*ld
   int attention(const T* q, long q_ld, const T* gate, long g_ld, T* out, long o_ld, int rows, int S, int H, const SegDesc* segs,
-                int nseg, bool causal, hipStream_t st, uint8_t* out8 = nullptr, long o8_ld = 0, float o8_inv = 0.f, int g_act = 0) {
+                int nseg, bool causal, hipStream_t st, uint8_t* out8 = nullptr, long o8_ld = 0, float o8_inv = 0.f, int g_act = 0,
+                const int* qlen = nullptr /* bf16: per-row query counts (AttnArgs.qlen), the joint attention of a length call */) {
     const int* nk = b_nkeys.as<int>();
     if constexpr (Num<T>::is_bf16) {
       AttnArgs a;
@@ -736,7 +730,7 @@ struct Engine : EngineBase {
       if (n == 0) return fail("attention without keys");
       CK(b_attn_redo.reserve((size_t)attn_redo_words(rows, H, S) * sizeof(int)));
       a.redo = b_attn_redo.as<int>();
-      a.qlen = attn_qlen;
+      a.qlen = qlen;
       if (profiling) {
         if (attn_events_used == attn_events.size()) {
           hipEvent_t e0, e1;
@@ -1249,16 +1243,15 @@ struct Engine : EngineBase {
     return ECHO_OK;
   }
   // host_nk rows must already describe this forward (set_row_keys)
-  // item_pos (host, B entries; nullptr: every item starts at start_pos): row r sees the latent-prefix keys of item r % B's own position
-  // item_len (host, B entries; nullptr: every item has S tokens): the self segment of row r ends at item r % B's own length
-  void set_row_keys(int rows, int B, int S, int start_pos, bool use_latent, const int32_t* ton, const int32_t* son, const int32_t* item_pos = nullptr,
-                    const int32_t* item_len = nullptr) {
+  // tabs.pos (nullptr: every item starts at start_pos): row r sees the latent-prefix keys of item r % B's own position
+  // tabs.len (nullptr: every item has S tokens): the self segment of row r ends at item r % B's own length
+  void set_row_keys(int rows, int B, int S, int start_pos, bool use_latent, const int32_t* ton, const int32_t* son, const ItemTables& tabs) {
     for (int r = 0; r < MAXROWS; ++r) {
       const int b = B > 0 ? r % B : 0;
       const bool in = r < rows;
-      host_nk[0 * MAXROWS + r] = in ? (item_len ? item_len[b] : S) : 0;
+      host_nk[0 * MAXROWS + r] = in ? (tabs.len ? tabs.len[b] : S) : 0;
       int nl = 0;
-      const int sp = item_pos ? item_pos[b] : start_pos;
+      const int sp = tabs.pos ? tabs.pos[b] : start_pos;
       if (in && use_latent && lat_T > 0) nl = std::min(lat_T, (sp + cfg.speaker_patch_size - 1) / cfg.speaker_patch_size);
       host_nk[1 * MAXROWS + r] = nl;
       host_nk[2 * MAXROWS + r] = (in && text_T > 0 && (!ton || ton[r])) ? text_nk[b] : 0;
@@ -1273,17 +1266,14 @@ struct Engine : EngineBase {
   struct ModSeg { int row0, nrows; const T* mod; };
 
   // xin (rows*S, lat_pad) -> vout (rows*S, 128); modrow = this step's [2L][3][D] modulation table (or `segs`: per-row-range tables)
-  // item_pos != nullptr: one start position per utterance; prepare_item_pos() has put the gathered RoPE rows of exactly these positions
+  // tabs.pos != nullptr: one start position per utterance; prepare_item_tables() has put the gathered RoPE rows of exactly these positions
   // into b_pos_rope (start_pos is then unused).  The RoPE consumers keep their arithmetic, base + m % modulus, on other arguments.
-  // item_len != nullptr (always with item_pos): per-utterance lengths.  The self key counts of set_row_keys are then also the bf16 attention's
+  // tabs.len != nullptr (always with tabs.pos): per-utterance lengths.  The self key counts of set_row_keys are then also the bf16 attention's
   // per-row query counts (AttnArgs.qlen): blocks of padding queries are written as zeros and cost no K / V work.
-  int forward_rows(int rows, int B, int S, int start_pos, bool use_latent, const T* modrow, hipStream_t st,
-                   const std::vector<ModSeg>* segs_in = nullptr, const int32_t* item_pos = nullptr, const int32_t* item_len = nullptr) {
-    struct QlenScope {     // attention() reads attn_qlen; every exit path of this forward puts it back
-      const int*& slot;
-      QlenScope(const int*& s, const int* v) : slot(s) { slot = v; }
-      ~QlenScope() { slot = nullptr; }
-    } qlen_scope(attn_qlen, item_len && Num<T>::is_bf16 ? b_nkeys.as<int>() : nullptr);
+  int forward_rows(int rows, int B, int S, int start_pos, bool use_latent, const T* modrow, hipStream_t st, const std::vector<ModSeg>* segs_in,
+                   const ItemTables& tabs) {
+    const bool item_pos = tabs.pos != nullptr;
+    const int* const qlen = tabs.len && Num<T>::is_bf16 ? b_nkeys.as<int>() : nullptr;
     const std::vector<ModSeg> one = {ModSeg{0, rows, modrow}};
     const std::vector<ModSeg>& segs = segs_in ? *segs_in : one;
     const int D = cfg.model_size, L = cfg.num_layers, H = cfg.num_heads, F = cfg.intermediate_size, M = rows * S;
@@ -1358,11 +1348,11 @@ struct Engine : EngineBase {
       if (st8) {
         CKI(fp8_reserve(M, std::max(D, F)));
         CK(b_h8.reserve((size_t)(M + 256) * F));
-        CKI(attention(qkvg, 4 * D, qkvg + 3 * D, 4 * D, ao, D, rows, S, H, sg, 4, false, st, b_q8.as<uint8_t>(), D, 1.0f / fp8_static[2 * l], gate_act));
+        CKI(attention(qkvg, 4 * D, qkvg + 3 * D, 4 * D, ao, D, rows, S, H, sg, 4, false, st, b_q8.as<uint8_t>(), D, 1.0f / fp8_static[2 * l], gate_act, qlen));
       } else if (!Num<T>::is_bf16 && item_pos && max_lat > 0) {
-        CKI(attention_by_prefix_width(qkvg, D, ao, rows, S, H, sg, gate_act, st));
+        CKI(attention_by_prefix_width(qkvg, D, ao, rows, S, H, sg, gate_act, st, qlen));
       } else {
-        CKI(attention(qkvg, 4 * D, qkvg + 3 * D, 4 * D, ao, D, rows, S, H, sg, 4, false, st, nullptr, 0, 0.f, gate_act));
+        CKI(attention(qkvg, 4 * D, qkvg + 3 * D, 4 * D, ao, D, rows, S, H, sg, 4, false, st, nullptr, 0, 0.f, gate_act, qlen));
       }
       for (const ModSeg& sgm : segs) {       // x += tanh(gate) * wo(attn): the gate is this segment's
         const long off = (long)sgm.row0 * S;
@@ -1415,7 +1405,8 @@ struct Engine : EngineBase {
   // rows are grouped by THEIR OWN prefix width rup(nl, 32) (0: no latent segment at all); one attention pass per width computes every row
   // with that layout and the rows of that width are kept.  One width (the usual case): one pass, as before.  The bf16 attention kernel
   // walks the segments per row and has no such dependence.
-  int attention_by_prefix_width(T* qkvg, int D, T* ao, int rows, int S, int H, const SegDesc* sg_in, int gate_act, hipStream_t st) {
+  int attention_by_prefix_width(T* qkvg, int D, T* ao, int rows, int S, int H, const SegDesc* sg_in, int gate_act, hipStream_t st,
+                                const int* qlen = nullptr) {
     std::map<int, int> width_maxk;      // width class -> largest key count in it
     for (int r = 0; r < rows; ++r) {
       const int nl = host_nk[1 * MAXROWS + r];
@@ -1423,12 +1414,12 @@ struct Engine : EngineBase {
       mk = std::max(mk, nl);
     }
     SegDesc sg[4] = {sg_in[0], sg_in[1], sg_in[2], sg_in[3]};
-    if (width_maxk.size() == 1) return attention(qkvg, 4 * D, qkvg + 3 * D, 4 * D, ao, D, rows, S, H, sg, 4, false, st, nullptr, 0, 0.f, gate_act);
+    if (width_maxk.size() == 1) return attention(qkvg, 4 * D, qkvg + 3 * D, 4 * D, ao, D, rows, S, H, sg, 4, false, st, nullptr, 0, 0.f, gate_act, qlen);
     const size_t row_bytes = (size_t)S * D * sizeof(T);
     CK(b_attn_keep.reserve((size_t)rows * row_bytes));
     for (const auto& wc : width_maxk) {
       sg[1].maxk = wc.second;
-      CKI(attention(qkvg, 4 * D, qkvg + 3 * D, 4 * D, ao, D, rows, S, H, sg, 4, false, st, nullptr, 0, 0.f, gate_act));
+      CKI(attention(qkvg, 4 * D, qkvg + 3 * D, 4 * D, ao, D, rows, S, H, sg, 4, false, st, nullptr, 0, 0.f, gate_act, qlen));
       for (int r = 0; r < rows; ++r)
         if ((int)rup(host_nk[1 * MAXROWS + r], 32) == wc.first)
           CK(hipMemcpyAsync((char*)b_attn_keep.p + r * row_bytes, (const char*)ao + r * row_bytes, row_bytes, hipMemcpyDeviceToDevice, st));
@@ -1474,50 +1465,37 @@ struct Engine : EngineBase {
     return ECHO_OK;
   }
 
-  // Per-utterance start positions (inference_blockwise.py:59-121 run for B streams that stand at different blocks).  Checks the table, sends
-  // it to the device through the staging ring and gathers the B * S RoPE rows the call's forwards read: once per call, in front of the
-  // step loop; no allocation and no synchronisation once the geometry is warm.
-  int prepare_item_pos(const int32_t* item_pos, int B, int S, hipStream_t st) {
-    if (!item_pos) return fail("per-utterance start positions: null position table");
-    if (B < 1 || 3 * B > MAXROWS || (size_t)B * sizeof(int32_t) > POS_TAB_BYTES) return fail("per-utterance start positions: at most 32 items per call (3 B <= 96 rows)");
-    if (S < 1) return fail("per-utterance start positions: bad sequence length");
-    if (!rope) return fail("rope table not set");
-    for (int b = 0; b < B; ++b) {
-      if (item_pos[b] < 0) return fail("per-utterance start positions: a start position is negative");
-      if ((long)item_pos[b] + S > rope_npos) return fail("per-utterance start positions: a start position plus S runs past the rope table (rope table too short)");
-    }
-    CK(b_pos_rope.reserve(POS_TAB_BYTES + (size_t)B * S * 64 * sizeof(float2)));
-    CK(stage_items.push(item_pos, (size_t)B * sizeof(int32_t), b_pos_rope.p, st));
-    CK(launch_rope_gather(rope, b_pos_rope.as<int>(), (float2*)((char*)b_pos_rope.p + POS_TAB_BYTES), B, S, st));
-    return ECHO_OK;
-  }
-
-  // Per-utterance lengths: item b has item_len[b] tokens of the call's S, the rest of its rows is padding.  Checks both tables
-  // (item_pos == nullptr: every item at fallback_pos), sends them to the device in ONE copy through the staging ring - start positions at the
-  // head of b_pos_rope's table, lengths at LEN_TAB_OFF - and gathers the call's RoPE rows; a padding token takes the row of its item's last
-  // valid position, so start + length is what has to fit the table.  Nothing is queued when a table is refused.
-  int prepare_item_len(const int32_t* item_pos, const int32_t* item_len, int fallback_pos, int B, int S, hipStream_t st) {
-    if (!item_len) return fail("per-utterance lengths: null length table");
-    if (fp8) return fail("per-utterance lengths: not supported by the fp8 engine (dit_fp8): its e4m3 attention output has no length form; use the bf16 engine");
-    if (B < 1 || 3 * B > MAXROWS || (size_t)(LEN_TAB_OFF + B) * sizeof(int32_t) > POS_TAB_BYTES || B > LEN_TAB_OFF) return fail("per-utterance lengths: at most 32 items per call (3 B <= 96 rows)");
-    if ((text_T > 0 && text_has_bias) || (spk_T > 0 && spk_has_bias))
-      return fail("per-utterance lengths: the text / speaker cache was built from a key mask that is not a prefix (per-key bias): the length forms of the "
-                  "attention exist for prefix masks only");
-    if (S < 1) return fail("per-utterance lengths: bad sequence length");
+  // Per-utterance start positions (inference_blockwise.py:59-121 run for B streams that stand at different blocks) and lengths (DESIGN.md 3.12:
+  // item b has item_len[b] tokens of the call's S, the rest of its rows is padding); at least one table is given.  A null position table means
+  // fallback_pos for every item, a null length table S tokens.  Checks the tables, writes the resolved positions to pos_out (B entries), sends
+  // both to the device in ONE copy through the staging ring - start positions at the head of b_pos_rope's table, lengths at LEN_TAB_OFF - and
+  // gathers the B * S RoPE rows the call's forwards read; a padding token takes the row of its item's last valid position, so start + length
+  // is what has to fit the table.  Once per call, in front of the step loop; no allocation and no synchronisation once the geometry is warm.
+  // Nothing is queued when a table is refused.  A refusal speaks of the tables the caller gave, and what only the length forms cannot do
+  // (the fp8 engine, a key mask that is not a prefix) is refused only for a length table.
+  int prepare_item_tables(const int32_t* item_pos, const int32_t* item_len, int fallback_pos, int B, int S, int32_t* pos_out, hipStream_t st) {
+    const std::string what = item_len ? "per-utterance lengths: " : "per-utterance start positions: ";
+    if (item_len && fp8) return fail(what + "not supported by the fp8 engine (dit_fp8): its e4m3 attention output has no length form; use the bf16 engine");
+    static_assert((LEN_TAB_OFF + ECHO_MAX_ITEMS) * sizeof(int32_t) <= POS_TAB_BYTES && ECHO_MAX_ITEMS <= LEN_TAB_OFF && 3 * ECHO_MAX_ITEMS == MAXROWS, "table layout");
+    if (B < 1 || B > ECHO_MAX_ITEMS) return fail(what + "at most 32 items per call (3 B <= 96 rows)");
+    if (item_len && ((text_T > 0 && text_has_bias) || (spk_T > 0 && spk_has_bias)))
+      return fail(what + "the text / speaker cache was built from a key mask that is not a prefix (per-key bias): the length forms of the "
+                         "attention exist for prefix masks only");
+    if (S < 1) return fail(what + "bad sequence length");
     if (!rope) return fail("rope table not set");
     int32_t tab[POS_TAB_BYTES / sizeof(int32_t)] = {};
     for (int b = 0; b < B; ++b) {
-      const int32_t sp = item_pos ? item_pos[b] : fallback_pos;
-      if (sp < 0) return fail("per-utterance lengths: a start position is negative");
-      if (item_len[b] < 1) return fail("per-utterance lengths: a length is below 1");
-      if (item_len[b] > S) return fail("per-utterance lengths: a length is above S");
-      if ((long)sp + item_len[b] > rope_npos) return fail("per-utterance lengths: a start position plus its length runs past the rope table (rope table too short)");
-      tab[b] = sp; tab[LEN_TAB_OFF + b] = item_len[b];
+      const int32_t sp = item_pos ? item_pos[b] : fallback_pos, n = item_len ? item_len[b] : S;
+      if (sp < 0) return fail(what + "a start position is negative");
+      if (n < 1) return fail(what + "a length is below 1");
+      if (n > S) return fail(what + "a length is above S");
+      if ((long)sp + n > rope_npos)
+        return fail(what + (item_len ? "a start position plus its length" : "a start position plus S") + " runs past the rope table (rope table too short)");
+      tab[b] = pos_out[b] = sp; tab[LEN_TAB_OFF + b] = n;
     }
-    len_pos.assign(tab, tab + B);
     CK(b_pos_rope.reserve(POS_TAB_BYTES + (size_t)B * S * 64 * sizeof(float2)));
     CK(stage_items.push(tab, POS_TAB_BYTES, b_pos_rope.p, st));
-    CK(launch_rope_gather_len(rope, b_pos_rope.as<int>(), len_dev(), (float2*)((char*)b_pos_rope.p + POS_TAB_BYTES), B, S, st));
+    CK(launch_rope_gather(rope, b_pos_rope.as<int>(), len_dev(), (float2*)((char*)b_pos_rope.p + POS_TAB_BYTES), B, S, st));
     return ECHO_OK;
   }
   // V^T of the self segment is [rows][D][rup(S, 64)]; the QKV tails write columns < S, and the attention's last key tile reads all 64 of its
@@ -1529,34 +1507,17 @@ struct Engine : EngineBase {
     CK(hipMemset2DAsync(b_vt_self.as<T>() + S, (size_t)Sp * sizeof(T), 0, (size_t)(Sp - S) * sizeof(T), (size_t)rows * cfg.model_size, st));
     return ECHO_OK;
   }
-  int dit_forward_len(const void* x, const void* temb, int n_t, const int32_t* row_t, int rows, int B, int S, const int32_t* item_pos,
-                      const int32_t* item_len, int use_latent, const int32_t* ton, const int32_t* son, float* v, hipStream_t st) override {
-    if (!dit_ready) return fail("echo_finalize_dit was not called");
-    if (!item_len) return fail("per-utterance lengths: null length table");
-    if (B < 1 || 3 * B > MAXROWS) return fail("per-utterance lengths: at most 32 items per call (3 B <= 96 rows)");
-    if (rows < 1 || rows > MAXROWS || rows % B || B != kvB) return fail("bad rows/B");
-    CKI(prepare_item_len(item_pos, item_len, 0, B, S, st));
-    return dit_forward_any(x, temb, n_t, row_t, rows, B, S, 0, len_pos.data(), use_latent, ton, son, v, st, item_len);
-  }
-
-  int dit_forward(const void* x, const void* temb, int n_t, const int32_t* row_t, int rows, int B, int S, int start_pos, int use_latent,
-                  const int32_t* ton, const int32_t* son, float* v, hipStream_t st) override {
-    return dit_forward_any(x, temb, n_t, row_t, rows, B, S, start_pos, nullptr, use_latent, ton, son, v, st);
-  }
-  int dit_forward_pos(const void* x, const void* temb, int n_t, const int32_t* row_t, int rows, int B, int S, const int32_t* item_pos,
-                      int use_latent, const int32_t* ton, const int32_t* son, float* v, hipStream_t st) override {
-    if (!dit_ready) return fail("echo_finalize_dit was not called");
-    if (!item_pos) return fail("per-utterance start positions: null position table");
-    if (B < 1 || 3 * B > MAXROWS) return fail("per-utterance start positions: at most 32 items per call (3 B <= 96 rows)");
-    if (rows < 1 || rows > MAXROWS || rows % B || B != kvB) return fail("bad rows/B");
-    CKI(prepare_item_pos(item_pos, B, S, st));
-    return dit_forward_any(x, temb, n_t, row_t, rows, B, S, 0, item_pos, use_latent, ton, son, v, st);
-  }
   // temb: (n_t, E) timestep embeddings; row_t (host, rows) = which of them each row uses (nullptr: all rows use embedding 0)
-  int dit_forward_any(const void* x, const void* temb, int n_t, const int32_t* row_t, int rows, int B, int S, int start_pos, const int32_t* item_pos,
-                      int use_latent, const int32_t* ton, const int32_t* son, float* v, hipStream_t st, const int32_t* item_len = nullptr) {
+  int dit_forward(const void* x, const void* temb, int n_t, const int32_t* row_t, int rows, int B, int S, int start_pos, const int32_t* item_pos,
+                  const int32_t* item_len, int use_latent, const int32_t* ton, const int32_t* son, float* v, hipStream_t st) override {
     if (!dit_ready) return fail("echo_finalize_dit was not called");
     if (rows < 1 || rows > MAXROWS || B < 1 || rows % B || B != kvB) return fail("bad rows/B");
+    int32_t pos[ECHO_MAX_ITEMS];
+    ItemTables tabs;
+    if (item_pos || item_len) {
+      CKI(prepare_item_tables(item_pos, item_len, start_pos, B, S, pos, st));
+      tabs.pos = pos; tabs.len = item_len;
+    }
     if (spk_T > 0 && (spkB < 1 || kvB % spkB)) return fail("the speaker cache's batch size must divide the text cache's");
     if (n_t < 1 || n_t > rows || (n_t > 1 && !row_t)) return fail("bad timestep table (1 <= n_t <= rows, row_t needed when n_t > 1)");
     const int M = rows * S;
@@ -1571,20 +1532,37 @@ struct Engine : EngineBase {
       if (!segs.empty() && segs.back().mod == mod) ++segs.back().nrows;
       else segs.push_back(ModSeg{r, 1, mod});
     }
-    set_row_keys(rows, B, S, start_pos, use_latent != 0, ton, son, item_pos, item_len);
+    set_row_keys(rows, B, S, start_pos, use_latent != 0, ton, son, tabs);
     CKI(push_nkeys(st));
-    if (item_len) {     // the caller's padding tokens are not read: zeros take their place, and zeros leave in v
+    // x (M, latent) -> xin (M, lat_pad) zero padded.  With lengths the caller's padding tokens are not read: zeros take their place, and zeros leave in v
+    if (tabs.len) {
       CK(launch_stage_x_len<T>((const T*)x, cfg.latent_size, b_xin.as<T>(), lat_pad, rows, B, S, len_dev(), st));
       CKI(clear_vt_tail(rows, S, st));
-      CKI(forward_rows(rows, B, S, start_pos, use_latent != 0, b_mod.as<T>(), st, &segs, item_pos, item_len));
-      CK(launch_convert_to_f32_len<T>(b_vout.as<T>(), 128, v, cfg.latent_size, rows, B, S, cfg.latent_size, len_dev(), st));
-      return ECHO_OK;
+    } else {
+      CK(hipMemcpy2DAsync(b_xin.p, lat_pad * sizeof(T), x, cfg.latent_size * sizeof(T), cfg.latent_size * sizeof(T), M, hipMemcpyDeviceToDevice, st));
     }
-    // x (M, latent) -> xin (M, lat_pad) zero padded
-    CK(hipMemcpy2DAsync(b_xin.p, lat_pad * sizeof(T), x, cfg.latent_size * sizeof(T), cfg.latent_size * sizeof(T), M,
-                        hipMemcpyDeviceToDevice, st));
-    CKI(forward_rows(rows, B, S, start_pos, use_latent != 0, b_mod.as<T>(), st, &segs, item_pos));
-    CK(launch_convert_to_f32<T>(b_vout.as<T>(), 128, v, cfg.latent_size, M, cfg.latent_size, st));
+    CKI(forward_rows(rows, B, S, start_pos, use_latent != 0, b_mod.as<T>(), st, &segs, tabs));
+    if (tabs.len) CK(launch_convert_to_f32_len<T>(b_vout.as<T>(), 128, v, cfg.latent_size, rows, B, S, cfg.latent_size, len_dev(), st));
+    else CK(launch_convert_to_f32<T>(b_vout.as<T>(), 128, v, cfg.latent_size, M, cfg.latent_size, st));
+    return ECHO_OK;
+  }
+
+  // profiling (echo_set_profiling) of a sampler call: ev[0] in front of it, ev[1] after the modulation tables (recorded by the call), ev[2] at its end
+  int prof_begin(hipStream_t st) {
+    if (!profiling) return ECHO_OK;
+    for (auto& e : ev) if (!e) CK(hipEventCreate(&e));
+    gemm_events_used = 0; attn_events_used = 0;
+    CK(hipEventRecord(ev[0], st));
+    return ECHO_OK;
+  }
+  int prof_end(hipStream_t st) {
+    if (!profiling) return ECHO_OK;
+    CK(hipEventRecord(ev[2], st));
+    CK(hipEventSynchronize(ev[2]));
+    CK(hipEventElapsedTime(&prof.ms_mod, ev[0], ev[1]));
+    CK(hipEventElapsedTime(&prof.ms_steps, ev[1], ev[2]));
+    prof.ms_total = prof.ms_mod + prof.ms_steps;
+    collect_gemm_times();
     return ECHO_OK;
   }
 
@@ -1598,18 +1576,14 @@ struct Engine : EngineBase {
     CKI(reserve_dit_ws(rows3 * S, rows3, S));
     CK(b_xstate.reserve((size_t)B * S * Lz * sizeof(float)));
     float* xs = b_xstate.as<float>();
-    if (profiling) {
-      for (auto& e : ev) if (!e) CK(hipEventCreate(&e));
-      gemm_events_used = 0; attn_events_used = 0;
-      CK(hipEventRecord(ev[0], st));
-    }
+    CKI(prof_begin(st));
     CK(hipMemcpyAsync(xs, x0, (size_t)B * S * Lz * sizeof(float), hipMemcpyDeviceToDevice, st));
     CKI(compute_mod((const T*)p->temb, N, st));
     if (profiling) CK(hipEventRecord(ev[1], st));
     // CFG row layout: rows [0,B) cond, [B,2B) text-uncond, [2B,3B) speaker-uncond (inference.py:474-475)
     std::vector<int32_t> ton(rows3, 1), son(rows3, 1);
     for (int b = 0; b < B; ++b) { ton[B + b] = 0; son[2 * B + b] = 0; }
-    set_row_keys(rows3, B, S, p->start_pos, p->use_latent != 0, ton.data(), son.data());
+    set_row_keys(rows3, B, S, p->start_pos, p->use_latent != 0, ton.data(), son.data(), ItemTables{});
     CKI(push_nkeys(st));
     const long modstride = (long)2 * cfg.num_layers * 3 * cfg.model_size;
     EulerArgs e;
@@ -1622,7 +1596,7 @@ struct Engine : EngineBase {
     for (int i = 0; i < N; ++i) {
       const echo_step& sp = p->steps[i];
       const int rows = sp.has_cfg ? rows3 : B;
-      CKI(forward_rows(rows, B, S, p->start_pos, p->use_latent != 0, b_mod.as<T>() + (long)i * modstride, st));
+      CKI(forward_rows(rows, B, S, p->start_pos, p->use_latent != 0, b_mod.as<T>() + (long)i * modstride, st, nullptr, ItemTables{}));
       if (sp.kv_unscale_after) CKI(scale_speaker_kv(1.0f / p->kv_scale, p->kv_max_layers, st));
       e.init = 0;
       e.R = sp.has_cfg ? 3 : 1;
@@ -1633,54 +1607,23 @@ struct Engine : EngineBase {
       CK(launch_euler<T>(e, st));
     }
     CK(hipMemcpyAsync(out, xs, (size_t)B * S * Lz * sizeof(float), hipMemcpyDeviceToDevice, st));
-    if (profiling) {
-      CK(hipEventRecord(ev[2], st));
-      CK(hipEventSynchronize(ev[2]));
-      CK(hipEventElapsedTime(&prof.ms_mod, ev[0], ev[1]));
-      CK(hipEventElapsedTime(&prof.ms_steps, ev[1], ev[2]));
-      prof.ms_total = prof.ms_mod + prof.ms_steps;
-      collect_gemm_times();
-    }
-    return ECHO_OK;
+    return prof_end(st);
   }
   // The same loop with per-utterance parameters (mixed batches).  `p` supplies B, S, num_steps, start_pos, use_latent and temb; every
   // item brings its own scales, truncation, KV scale and step table.  A step runs the 3B-row CFG layout when ANY item has CFG at
   // it (the `row % B` KV addressing stays), so items outside their window ride along in the un-conditional rows.
-  int sample_euler_items(const echo_sampler_params* p, const echo_sampler_item* items, const float* x0, float* out, hipStream_t st) override {
-    return sample_euler_items_any(p, items, nullptr, false, x0, out, st);
-  }
-  int sample_euler_items_pos(const echo_sampler_params* p, const echo_sampler_item* items, const int32_t* item_pos, const float* x0, float* out,
-                             hipStream_t st) override {
-    if (!item_pos) return fail("per-utterance start positions: null position table");
-    if (p && (p->B < 1 || 3 * p->B > MAXROWS)) return fail("per-utterance start positions: at most 32 items per call (3 B <= 96 rows)");
-    return sample_euler_items_any(p, items, item_pos, true, x0, out, st);
-  }
-  int sample_euler_items_len(const echo_sampler_params* p, const echo_sampler_item* items, const int32_t* item_pos, const int32_t* item_len,
-                             const float* x0, float* out, hipStream_t st) override {
-    if (!item_len) return fail("per-utterance lengths: null length table");
-    if (p && (p->B < 1 || 3 * p->B > MAXROWS)) return fail("per-utterance lengths: at most 32 items per call (3 B <= 96 rows)");
-    return sample_euler_items_any(p, items, item_pos, true, x0, out, st, item_len);
-  }
-  // Per-utterance step counts: item b runs item_steps[b] <= p->num_steps steps of its own schedule and is left alone afterwards.
-  int sample_euler_items_steps(const echo_sampler_params* p, const echo_sampler_item* items, const int32_t* item_steps, const int32_t* item_pos,
-                               const int32_t* item_len, const float* x0, float* out, hipStream_t st) override {
-    if (!item_steps) return fail("per-utterance step counts: null step-count table");
-    if (fp8) return fail("per-utterance step counts: not supported by the fp8 engine (dit_fp8): the call builds on the length tables, which its e4m3 attention output has no form for; use the bf16 engine");
-    if (p && (p->B < 1 || 3 * p->B > MAXROWS)) return fail("per-utterance step counts: at most 32 items per call (3 B <= 96 rows)");
-    return sample_euler_items_any(p, items, item_pos, item_pos != nullptr || item_len != nullptr, x0, out, st, item_len, item_steps);
-  }
-  // with_pos: p->start_pos is ignored, item b starts at item_pos[b] (host, B entries)
-  // item_len (host, B entries, with_pos): per-utterance lengths; item_pos may then be null (p->start_pos for every item).  The length forms of
-  // the staging and update kernels run instead of the memcpy and euler_items_kernel: x_t of a padding token is 0 from the first launch on.
+  // item_pos (host, B entries): p->start_pos is ignored, item b starts at item_pos[b].
+  // item_len (host, B entries): per-utterance lengths; item_pos may then be null (p->start_pos for every item).  x_t of a padding token is 0
+  // from the first launch on.
   // item_steps (host, B entries): per-utterance step counts.  N = p->num_steps is the call's maximum; item b is ACTIVE in iteration i
   // while i < item_steps[b] and takes step i of its own table (item_steps[b] entries), FINISHED afterwards.  The distinct counts, in order of first
   // appearance, are the call's groups (at most MAX_STEP_GROUPS); p->temb is [N][G], entry [i][g] the embedding of group g's i-th timestep (entries
   // with i >= the group's count are not used; they must be finite).  A forward gets one ModSeg per run of adjacent rows of one group - the caller
   // orders the items so that groups are contiguous: at most 3 G segments - and a finished item's rows use the modulation of its group's last step, so
-  // that everything they leave in the workspace stays finite.  The *_steps update kernels run instead of euler_items(_len)_kernel.
+  // that everything they leave in the workspace stays finite.  Its table entries carry `done`: euler_items_kernel leaves its x_t alone.
   static constexpr int MAX_STEP_GROUPS = 8;
-  int sample_euler_items_any(const echo_sampler_params* p, const echo_sampler_item* items, const int32_t* item_pos, bool with_pos, const float* x0,
-                             float* out, hipStream_t st, const int32_t* item_len = nullptr, const int32_t* item_steps = nullptr) {
+  int sample_euler_items(const echo_sampler_params* p, const echo_sampler_item* items, const int32_t* item_pos, const int32_t* item_len,
+                         const int32_t* item_steps, const float* x0, float* out, hipStream_t st) override {
     if (!dit_ready) return fail("echo_finalize_dit was not called");
     if (!p || !items) return fail("mixed sampler call: null params / items");
     const int B = p->B, S = p->S, N = p->num_steps, Lz = cfg.latent_size;
@@ -1747,22 +1690,19 @@ struct Engine : EngineBase {
       if (has_unscale[i]) CKI(kv_slot_scales(us.data(), ul.data(), B, unscale[i]));
     }
     if (item_steps) steps_ignore_done = false;      // the test instrument is one-shot: this call's table has consumed it
-    if (item_len) {
-      CKI(prepare_item_len(item_pos, item_len, p->start_pos, B, S, st));
-      item_pos = len_pos.data();
-    } else
-    if (with_pos) CKI(prepare_item_pos(item_pos, B, S, st));      // refuses a null table / a position past the rope table before any work is queued
+    int32_t pos[ECHO_MAX_ITEMS];
+    ItemTables tabs;
+    if (item_pos || item_len) {      // refuses a position past the rope table before any work is queued
+      CKI(prepare_item_tables(item_pos, item_len, p->start_pos, B, S, pos, st));
+      tabs.pos = pos; tabs.len = item_len;
+    }
     const int rows3 = 3 * B;
     CKI(reserve_dit_ws(rows3 * S, rows3, S));
     CK(b_xstate.reserve((size_t)B * S * Lz * sizeof(float)));
     const size_t tab_bytes = tab.size() * sizeof(EulerItem), init_bytes = (size_t)B * sizeof(float);
     CK(b_items.reserve(tab_bytes + init_bytes));
     float* xs = b_xstate.as<float>();
-    if (profiling) {
-      for (auto& e : ev) if (!e) CK(hipEventCreate(&e));
-      gemm_events_used = 0; attn_events_used = 0;
-      CK(hipEventRecord(ev[0], st));
-    }
+    CKI(prof_begin(st));
     {   // one copy: [N][B] step entries, then the B init scales
       std::vector<char> blob(tab_bytes + init_bytes);
       memcpy(blob.data(), tab.data(), tab_bytes);
@@ -1770,13 +1710,12 @@ struct Engine : EngineBase {
       CK(stage_items.push(blob.data(), blob.size(), b_items.p, st));
     }
     const EulerItem* tab_dev = b_items.as<EulerItem>();
-    if (!item_len) CK(hipMemcpyAsync(xs, x0, (size_t)B * S * Lz * sizeof(float), hipMemcpyDeviceToDevice, st));
-    else CKI(clear_vt_tail(rows3, S, st));
+    if (tabs.len) CKI(clear_vt_tail(rows3, S, st));
     CKI(compute_mod((const T*)p->temb, N * G, st));
     if (profiling) CK(hipEventRecord(ev[1], st));
     std::vector<int32_t> ton(rows3, 1), son(rows3, 1);
     for (int b = 0; b < B; ++b) { ton[B + b] = 0; son[2 * B + b] = 0; }
-    set_row_keys(rows3, B, S, p->start_pos, p->use_latent != 0, ton.data(), son.data(), with_pos ? item_pos : nullptr, item_len);
+    set_row_keys(rows3, B, S, p->start_pos, p->use_latent != 0, ton.data(), son.data(), tabs);
     CKI(push_nkeys(st));
     const long modstride = (long)2 * cfg.num_layers * 3 * cfg.model_size;
     EulerItemsArgs e;
@@ -1785,13 +1724,8 @@ struct Engine : EngineBase {
     e.B = B; e.S = S; e.L = Lz; e.R = 1;
     e.R_next = any_cfg[0] ? 3 : 1;
     e.init = 1; e.init_scale = (const float*)((const char*)b_items.p + tab_bytes); e.items = tab_dev;
-    auto update = [&]() -> hipError_t {
-      if (!item_len) return item_steps ? launch_euler_items_steps<T>(e, st) : launch_euler_items<T>(e, st);
-      EulerItemsLenArgs el;
-      el.a = e; el.len = len_dev(); el.x0 = x0;
-      return item_steps ? launch_euler_items_steps_len<T>(el, st) : launch_euler_items_len<T>(el, st);
-    };
-    CK(update());
+    e.x0 = x0; e.len = tabs.len ? len_dev() : nullptr;      // the init launch reads the caller's x_init itself and writes every x_t
+    CK(launch_euler_items<T>(e, st));
     std::vector<ModSeg> segs;
     for (int i = 0; i < N; ++i) {
       const int rows = any_cfg[i] ? rows3 : B;
@@ -1804,25 +1738,16 @@ struct Engine : EngineBase {
           else segs.push_back(ModSeg{r, 1, mod});
         }
       }
-      CKI(forward_rows(rows, B, S, p->start_pos, p->use_latent != 0, b_mod.as<T>() + (long)i * modstride, st, item_steps ? &segs : nullptr,
-                       with_pos ? item_pos : nullptr, item_len));
+      CKI(forward_rows(rows, B, S, p->start_pos, p->use_latent != 0, b_mod.as<T>() + (long)i * modstride, st, item_steps ? &segs : nullptr, tabs));
       if (has_unscale[i]) CKI(launch_kv_slot_scales(unscale[i], st));
       e.init = 0;
       e.R = any_cfg[i] ? 3 : 1;
       e.R_next = (i + 1 < N && any_cfg[i + 1]) ? 3 : 1;
       e.items = tab_dev + (size_t)i * B;
-      CK(update());
+      CK(launch_euler_items<T>(e, st));
     }
     CK(hipMemcpyAsync(out, xs, (size_t)B * S * Lz * sizeof(float), hipMemcpyDeviceToDevice, st));
-    if (profiling) {
-      CK(hipEventRecord(ev[2], st));
-      CK(hipEventSynchronize(ev[2]));
-      CK(hipEventElapsedTime(&prof.ms_mod, ev[0], ev[1]));
-      CK(hipEventElapsedTime(&prof.ms_steps, ev[1], ev[2]));
-      prof.ms_total = prof.ms_mod + prof.ms_steps;
-      collect_gemm_times();
-    }
-    return ECHO_OK;
+    return prof_end(st);
   }
   void collect_gemm_times() {
     prof.ms_gemm_sum = 0.f; prof.n_gemm = 0; prof.ms_pp_sum = 0.f; prof.n_pp = 0; prof.flops_pp = 0.0;
@@ -2831,11 +2756,11 @@ int echo_scale_speaker_kv(echo_ctx* ctx, float scale, int max_layers, void* stre
 }
 int echo_dit_forward(echo_ctx* ctx, const void* x, const void* temb, int rows, int B, int S, int start_pos, int use_latent,
                      const int32_t* ton, const int32_t* son, float* v_out, void* stream) {
-  return ctx ? ctx->eng->dit_forward(x, temb, 1, nullptr, rows, B, S, start_pos, use_latent, ton, son, v_out, (hipStream_t)stream) : ECHO_ERR;
+  return ctx ? ctx->eng->dit_forward(x, temb, 1, nullptr, rows, B, S, start_pos, nullptr, nullptr, use_latent, ton, son, v_out, (hipStream_t)stream) : ECHO_ERR;
 }
 int echo_dit_forward_t(echo_ctx* ctx, const void* x, const void* temb, int n_t, const int32_t* row_t, int rows, int B, int S, int start_pos,
                        int use_latent, const int32_t* ton, const int32_t* son, float* v_out, void* stream) {
-  return ctx ? ctx->eng->dit_forward(x, temb, n_t, row_t, rows, B, S, start_pos, use_latent, ton, son, v_out, (hipStream_t)stream) : ECHO_ERR;
+  return ctx ? ctx->eng->dit_forward(x, temb, n_t, row_t, rows, B, S, start_pos, nullptr, nullptr, use_latent, ton, son, v_out, (hipStream_t)stream) : ECHO_ERR;
 }
 int echo_sample_euler(echo_ctx* ctx, const echo_sampler_params* p, const float* x_init, float* latent_out, void* stream) {
   return ctx ? ctx->eng->sample_euler(p, x_init, latent_out, (hipStream_t)stream) : ECHO_ERR;
@@ -2903,33 +2828,65 @@ int echo_voice_bind_items(echo_ctx* ctx, const echo_voice* const* voices, int n,
   }
   return ctx->eng->voice_bind_items(vs, n, (hipStream_t)stream);
 }
+// The per-utterance entry points are adapters of EngineBase::dit_forward / sample_euler_items.  Each refuses in its own words what is its own
+// to refuse - the table it exists for being null, more than 32 items - and hands its tables on.
+static const char* const POS_CALL = "per-utterance start positions: ";
+static const char* const LEN_CALL = "per-utterance lengths: ";
+static const char* const STEPS_CALL = "per-utterance step counts: ";
+static int too_many_items(EngineBase* e, const char* call) { return e->fail(std::string(call) + "at most 32 items per call (3 B <= 96 rows)"); }
+static bool items_in_range(int B) { return B >= 1 && B <= ECHO_MAX_ITEMS; }
+
 int echo_dit_forward_pos(echo_ctx* ctx, const void* x, const void* temb, int n_t, const int32_t* row_t, int rows, int B, int S,
                          const int32_t* item_start_pos, int use_latent, const int32_t* ton, const int32_t* son, float* v_out, void* stream) {
-  return ctx ? ctx->eng->dit_forward_pos(x, temb, n_t, row_t, rows, B, S, item_start_pos, use_latent, ton, son, v_out, (hipStream_t)stream) : ECHO_ERR;
-}
-int echo_sample_euler_items_pos(echo_ctx* ctx, const echo_sampler_params* p, const echo_sampler_item* items, const int32_t* item_start_pos,
-                                const float* x_init, float* latent_out, void* stream) {
-  return ctx ? ctx->eng->sample_euler_items_pos(p, items, item_start_pos, x_init, latent_out, (hipStream_t)stream) : ECHO_ERR;
+  if (!ctx) return ECHO_ERR;
+  EngineBase* e = ctx->eng.get();
+  if (!e->dit_ready) return e->fail("echo_finalize_dit was not called");
+  if (!item_start_pos) return e->fail(std::string(POS_CALL) + "null position table");
+  if (!items_in_range(B)) return too_many_items(e, POS_CALL);
+  return e->dit_forward(x, temb, n_t, row_t, rows, B, S, 0, item_start_pos, nullptr, use_latent, ton, son, v_out, (hipStream_t)stream);
 }
 int echo_dit_forward_len(echo_ctx* ctx, const void* x, const void* temb, int n_t, const int32_t* row_t, int rows, int B, int S,
                          const int32_t* item_start_pos, const int32_t* item_len, int use_latent, const int32_t* ton, const int32_t* son, float* v_out,
                          void* stream) {
-  return ctx ? ctx->eng->dit_forward_len(x, temb, n_t, row_t, rows, B, S, item_start_pos, item_len, use_latent, ton, son, v_out, (hipStream_t)stream) : ECHO_ERR;
-}
-int echo_sample_euler_items_len(echo_ctx* ctx, const echo_sampler_params* p, const echo_sampler_item* items, const int32_t* item_start_pos,
-                                const int32_t* item_len, const float* x_init, float* latent_out, void* stream) {
-  return ctx ? ctx->eng->sample_euler_items_len(p, items, item_start_pos, item_len, x_init, latent_out, (hipStream_t)stream) : ECHO_ERR;
-}
-int echo_scale_speaker_kv_items(echo_ctx* ctx, const float* scales_host, const int32_t* max_layers_host, int n, void* stream) {
-  return ctx ? ctx->eng->scale_speaker_kv_items(scales_host, max_layers_host, n, (hipStream_t)stream) : ECHO_ERR;
-}
-int echo_sample_euler_items_steps(echo_ctx* ctx, const echo_sampler_params* p, const echo_sampler_item* items, const int32_t* item_steps,
-                                  const int32_t* item_start_pos, const int32_t* item_len, const float* x_init, float* latent_out, void* stream) {
-  return ctx ? ctx->eng->sample_euler_items_steps(p, items, item_steps, item_start_pos, item_len, x_init, latent_out, (hipStream_t)stream) : ECHO_ERR;
+  if (!ctx) return ECHO_ERR;
+  EngineBase* e = ctx->eng.get();
+  if (!e->dit_ready) return e->fail("echo_finalize_dit was not called");
+  if (!item_len) return e->fail(std::string(LEN_CALL) + "null length table");
+  if (!items_in_range(B)) return too_many_items(e, LEN_CALL);
+  return e->dit_forward(x, temb, n_t, row_t, rows, B, S, 0, item_start_pos, item_len, use_latent, ton, son, v_out, (hipStream_t)stream);
 }
 int echo_sample_euler_items(echo_ctx* ctx, const echo_sampler_params* p, const echo_sampler_item* items, const float* x_init, float* latent_out,
                             void* stream) {
-  return ctx ? ctx->eng->sample_euler_items(p, items, x_init, latent_out, (hipStream_t)stream) : ECHO_ERR;
+  return ctx ? ctx->eng->sample_euler_items(p, items, nullptr, nullptr, nullptr, x_init, latent_out, (hipStream_t)stream) : ECHO_ERR;
+}
+int echo_sample_euler_items_pos(echo_ctx* ctx, const echo_sampler_params* p, const echo_sampler_item* items, const int32_t* item_start_pos,
+                                const float* x_init, float* latent_out, void* stream) {
+  if (!ctx) return ECHO_ERR;
+  EngineBase* e = ctx->eng.get();
+  if (!item_start_pos) return e->fail(std::string(POS_CALL) + "null position table");
+  if (p && !items_in_range(p->B)) return too_many_items(e, POS_CALL);
+  return e->sample_euler_items(p, items, item_start_pos, nullptr, nullptr, x_init, latent_out, (hipStream_t)stream);
+}
+int echo_sample_euler_items_len(echo_ctx* ctx, const echo_sampler_params* p, const echo_sampler_item* items, const int32_t* item_start_pos,
+                                const int32_t* item_len, const float* x_init, float* latent_out, void* stream) {
+  if (!ctx) return ECHO_ERR;
+  EngineBase* e = ctx->eng.get();
+  if (!item_len) return e->fail(std::string(LEN_CALL) + "null length table");
+  if (p && !items_in_range(p->B)) return too_many_items(e, LEN_CALL);
+  return e->sample_euler_items(p, items, item_start_pos, item_len, nullptr, x_init, latent_out, (hipStream_t)stream);
+}
+// Per-utterance step counts: item b runs item_steps[b] <= p->num_steps steps of its own schedule and is left alone afterwards.
+int echo_sample_euler_items_steps(echo_ctx* ctx, const echo_sampler_params* p, const echo_sampler_item* items, const int32_t* item_steps,
+                                  const int32_t* item_start_pos, const int32_t* item_len, const float* x_init, float* latent_out, void* stream) {
+  if (!ctx) return ECHO_ERR;
+  EngineBase* e = ctx->eng.get();
+  if (!item_steps) return e->fail(std::string(STEPS_CALL) + "null step-count table");
+  if (e->fp8) return e->fail(std::string(STEPS_CALL) + "not supported by the fp8 engine (dit_fp8): the call builds on the length tables, which its e4m3 attention output has no form for; use the bf16 engine");
+  if (p && !items_in_range(p->B)) return too_many_items(e, STEPS_CALL);
+  return e->sample_euler_items(p, items, item_start_pos, item_len, item_steps, x_init, latent_out, (hipStream_t)stream);
+}
+int echo_scale_speaker_kv_items(echo_ctx* ctx, const float* scales_host, const int32_t* max_layers_host, int n, void* stream) {
+  return ctx ? ctx->eng->scale_speaker_kv_items(scales_host, max_layers_host, n, (hipStream_t)stream) : ECHO_ERR;
 }
 int64_t echo_voice_bytes(const echo_voice* voice) {
   return voice && voice->v ? (int64_t)(voice->v->kv_bytes + voice->v->vt_bytes + voice->v->bias_bytes) : 0;

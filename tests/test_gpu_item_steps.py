@@ -129,19 +129,19 @@ def test_entry_point_is_bound():
 
 
 # ------------------------------------------------------------------------------------------------ 1. equal counts
-@pytest.mark.parametrize("with_pos", [False, True])
+@pytest.mark.parametrize("positions", [False, True])
 @pytest.mark.parametrize("engine", ENGINES)
-def test_equal_counts_give_the_bits_of_the_length_call(tiny_models, engine, with_pos):
+def test_equal_counts_give_the_bits_of_the_length_call(tiny_models, engine, positions):
     """B = 3, S = 32, counts (6, 6, 6), three parameter sets: torch.equal with echo_sample_euler_items_len on the same inputs (full and ragged
     lengths), with a position table and with NULL (every item at p->start_pos); without a length table, with the plain / position call."""
     c = Call(tiny_models[engine], 3)
     items = _params([6, 6, 6])
-    pos, sp = ([0, 13, 5], 0) if with_pos else (None, 13)
+    pos, sp = ([0, 13, 5], 0) if positions else (None, 13)
     for lengths in ([32, 32, 32], [32, 20, 9]):
         want = c.existing(items, pos=pos, lengths=lengths, start_pos=sp)
         got = c.steps(items, [6, 6, 6], pos=pos, lengths=lengths, start_pos=sp)
         assert bool(torch.isfinite(want).all()) and float(want.abs().max()) > 0
-        assert torch.equal(got, want), (engine, with_pos, lengths)
+        assert torch.equal(got, want), (engine, positions, lengths)
     want = c.existing(items, pos=pos, start_pos=sp)
     assert torch.equal(c.steps(items, [6, 6, 6], pos=pos, start_pos=sp), want)
 
@@ -165,8 +165,8 @@ def _frozen(c, counts, form):
 @pytest.mark.parametrize("engine", ENGINES)
 def test_a_finished_item_is_frozen(tiny_models, engine, form):
     """B = 3, S = 32, counts (6, 4, 2), parameter sets cfg_default / cfg_off / all_options (its speaker-KV un-scaling fires at its own step):
-    latent_out of item b equals, bit for bit, its row in the call of counts (n_b, n_b, n_b) - same B, S, tables of b.  Both update kernels
-    (euler_items_steps_kernel; its length form with ragged lengths and a position table)."""
+    latent_out of item b equals, bit for bit, its row in the call of counts (n_b, n_b, n_b) - same B, S, tables of b.  Both forms of the
+    update (euler_items_kernel without a length table; with ragged lengths and a position table)."""
     _frozen(Call(tiny_models[engine], 3), [6, 4, 2], form)
 
 

@@ -101,6 +101,57 @@ def _uniform_equals_existing(g, m, p):
     assert bool(torch.isfinite(sa).all()) and torch.equal(sa, sb)
 
 
+@pytest.mark.parametrize("engine", ENGINES)
+def test_position_call_ending_on_the_last_rope_row(tiny_models, engine):
+    """A position-only call reads its RoPE rows through the gather that clamps at an item's length, with every length S.  B = 2, S = 32, item 0 at
+    0, item 1 at 13, and a RoPE table of exactly 13 + 32 rows (the model's own table, announced that short): item 1's last token reads the last
+    row.  Each item of echo_dit_forward_pos / echo_sample_euler_items_pos has the bits of echo_dit_forward_t / echo_sample_euler_items with
+    start_pos at that item's position (same B, caches and noise).  One position more is refused ("rope table") and writes nothing."""
+    m = tiny_models[engine]
+    B, S, P1 = 2, 32, 13
+    positions = [0, P1]
+    ids, tm, spk, sm, prefix, x, tm3, sm3 = _inputs(B, S, 16)
+    kvt, kvs, kvl = _caches(m, ids, tm, spk, sm, prefix)
+    t = torch.full((3 * B,), 0.7)
+    xx = x.to(m.dtype)
+    arr, temb, _keep = inf.build_sampler_items(m, [dict(SAMPLER_CASES["cfg_default"], rng_seed=0), dict(SAMPLER_CASES["cfg_default"], rng_seed=0, cfg_scale_text=2.0)])
+    x0 = x[:B].to(DEV).contiguous()
+    lib, ctx = m._lib, m._ctx
+    L.check(lib.echo_set_rope_table(ctx, m._rope.data_ptr(), P1 + S), ctx)
+    try:
+        fwd = m(xx, t, tm3, sm3, kvt, kvs, start_pos=positions, kv_cache_latent=kvl)
+        lat = inf.run_euler_items(m, x0, arr, 6, temb, start_pos=positions, use_latent=True)
+        assert bool(torch.isfinite(fwd).all()) and bool(torch.isfinite(lat).all()) and float(lat.abs().max()) > 0
+        for b, p in enumerate(positions):
+            rows = [b, B + b, 2 * B + b]         # item b's cond / text-uncond / speaker-uncond rows
+            uni = m(xx, t, tm3, sm3, kvt, kvs, start_pos=p, kv_cache_latent=kvl)
+            assert torch.equal(fwd[rows], uni[rows]), (engine, "forward", b, p)
+            assert not torch.equal(fwd[[1 - b]], uni[[1 - b]])         # teeth: the other item stands elsewhere
+            ulat = inf.run_euler_items(m, x0, arr, 6, temb, start_pos=p, use_latent=True)
+            assert torch.equal(lat[b], ulat[b]), (engine, "sampler", b, p)
+            assert not torch.equal(lat[1 - b], ulat[1 - b])
+        # one position more: refused before anything is queued
+        past = (C.c_int32 * B)(0, P1 + 1)
+        SENTINEL = 12345.0
+        temb1 = torch.zeros((1, TINY.timestep_embed_size), dtype=m.dtype, device=DEV)
+        out = torch.full((3 * B, S, 80), SENTINEL, dtype=torch.float32, device=DEV)
+        on = (C.c_int32 * (3 * B))(*([1] * (3 * B)))
+        xd = xx.to(DEV).contiguous()
+        rc = lib.echo_dit_forward_pos(ctx, xd.data_ptr(), temb1.data_ptr(), 1, None, 3 * B, B, S, past, 1, on, on, out.data_ptr(), m._stream())
+        assert rc != 0 and b"rope table" in lib.echo_last_error(ctx)
+        p = L.EchoSamplerParams()
+        p.B, p.S, p.num_steps, p.use_latent = B, S, 6, 1
+        td = temb.to(DEV).contiguous()
+        p.temb = td.data_ptr()
+        o2 = torch.full_like(x0, SENTINEL)
+        rc = lib.echo_sample_euler_items_pos(ctx, C.byref(p), arr, past, x0.data_ptr(), o2.data_ptr(), m._stream())
+        assert rc != 0 and b"rope table" in lib.echo_last_error(ctx)
+        torch.cuda.synchronize()
+        assert bool((out == SENTINEL).all()) and bool((o2 == SENTINEL).all())
+    finally:
+        L.check(lib.echo_set_rope_table(ctx, m._rope.data_ptr(), m.MAX_POS), ctx)
+
+
 # ------------------------------------------------------------------------------------------------ 2. staggered == uniform per item
 def _staggered_equals_uniform(m, B, S, positions):
     assert len(positions) == B
