@@ -162,6 +162,12 @@ SIGNATURES = {
     "echo_sample_euler_items_steps": (C.c_int, [vp, C.POINTER(EchoSamplerParams), C.POINTER(EchoSamplerItem), C.POINTER(C.c_int32),
                                                 C.POINTER(C.c_int32), C.POINTER(C.c_int32), vp, vp, vp]),
     "echo_debug_item_steps_ignore_done": (C.c_int, [vp, C.c_int]),
+    "echo_dit_forward_rows": (C.c_int, [vp, vp, vp, C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32),
+                                        C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), vp, vp]),
+    "echo_sample_euler_items_compact": (C.c_int, [vp, C.POINTER(EchoSamplerParams), C.POINTER(EchoSamplerItem), C.POINTER(C.c_int32),
+                                                  C.POINTER(C.c_int32), C.POINTER(C.c_int32), vp, vp, vp]),
+    "echo_debug_last_row_forwards": (c_i64, [vp]),
+    "echo_op_attention_bf16_rows": (C.c_int, [C.POINTER(EchoAttnDesc), vp, vp, vp]),
     "echo_scale_speaker_kv_items": (C.c_int, [vp, C.POINTER(C.c_float), C.POINTER(C.c_int32), C.c_int, vp]),
     "echo_voice_bind_items": (C.c_int, [vp, C.POINTER(vp), C.c_int, vp]),
     "echo_voice_bytes": (c_i64, [vp]),

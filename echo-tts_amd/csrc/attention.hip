@@ -125,13 +125,15 @@ __device__ __forceinline__ void attn_body(const AttnArgs& p, char* const smem, c
 #pragma unroll
   for (int sgi = 0; sgi < 4; ++sgi)
     if (sgi < p.nseg && mod0 == 0 && p.seg[sgi].kv_mod > 0) mod0 = p.seg[sgi].kv_mod;
-  const int rmod0 = mod0 > 0 ? row % mod0 : row;
+  // row map (AttnArgs.row_item): the shared-KV segments take the row's ITEM; one wave-uniform scalar read per workgroup
+  const int item = p.row_item ? __builtin_amdgcn_readfirstlane(p.row_item[row]) : row;
+  const int rmod0 = mod0 > 0 ? item % mod0 : row;
 #pragma unroll
   for (int sgi = 0; sgi < 4; ++sgi) {
     kb_[sgi] = nullptr; vb_[sgi] = nullptr; kld_[sgi] = 0; vld_[sgi] = 0; bias_[sgi] = nullptr;
     if (sgi < p.nseg) {
       const AttnSeg& sg = p.seg[sgi];
-      const int kvrow = sg.kv_mod == 0 ? row : (sg.kv_mod == mod0 ? rmod0 : row % sg.kv_mod);   // one division per workgroup in practice
+      const int kvrow = sg.kv_mod == 0 ? row : (sg.kv_mod == mod0 ? rmod0 : item % sg.kv_mod);   // one division per workgroup in practice
       kb_[sgi] = (const char*)(sg.K + (long)kvrow * sg.k_row_stride + (long)head * sg.k_head_stride);
       vb_[sgi] = (const char*)(sg.Vt + (long)kvrow * sg.vt_row_stride + (long)head * sg.vt_head_stride);
       kld_[sgi] = sg.k_ld * 2; vld_[sgi] = sg.vt_ld * 2;
@@ -599,13 +601,15 @@ __global__ void __launch_bounds__(256, 1) attn4_kernel(const AttnArgs p) {
 #pragma unroll
   for (int sgi = 0; sgi < 4; ++sgi)
     if (sgi < p.nseg && mod0 == 0 && p.seg[sgi].kv_mod > 0) mod0 = p.seg[sgi].kv_mod;
-  const int rmod0 = mod0 > 0 ? row % mod0 : row;
+  // row map (AttnArgs.row_item): the shared-KV segments take the row's ITEM; one wave-uniform scalar read per workgroup
+  const int item = p.row_item ? __builtin_amdgcn_readfirstlane(p.row_item[row]) : row;
+  const int rmod0 = mod0 > 0 ? item % mod0 : row;
 #pragma unroll
   for (int sgi = 0; sgi < 4; ++sgi) {
     kb_[sgi] = nullptr; vb_[sgi] = nullptr; kld_[sgi] = 0; vld_[sgi] = 0;
     if (sgi < p.nseg) {
       const AttnSeg& sg = p.seg[sgi];
-      const int kvrow = sg.kv_mod == 0 ? row : (sg.kv_mod == mod0 ? rmod0 : row % sg.kv_mod);
+      const int kvrow = sg.kv_mod == 0 ? row : (sg.kv_mod == mod0 ? rmod0 : item % sg.kv_mod);
       kb_[sgi] = (const char*)(sg.K + (long)kvrow * sg.k_row_stride + (long)head * sg.k_head_stride);
       vb_[sgi] = (const char*)(sg.Vt + (long)kvrow * sg.vt_row_stride + (long)head * sg.vt_head_stride);
       kld_[sgi] = sg.k_ld * 2; vld_[sgi] = sg.vt_ld * 2;
@@ -1021,12 +1025,14 @@ __device__ __forceinline__ void attn5_body(const AttnArgs& p) {
 #pragma unroll
   for (int sgi = 0; sgi < 4; ++sgi)
     if (sgi < p.nseg && mod0 == 0 && p.seg[sgi].kv_mod > 0) mod0 = p.seg[sgi].kv_mod;
-  const int rmod0 = mod0 > 0 ? row % mod0 : row;
+  // row map (AttnArgs.row_item): the shared-KV segments take the row's ITEM; one wave-uniform scalar read per workgroup
+  const int item = !(DIAG & 256) && p.row_item ? __builtin_amdgcn_readfirstlane(p.row_item[row]) : row;      // (the e4m3 output has no row-map form)
+  const int rmod0 = mod0 > 0 ? item % mod0 : row;
 #pragma unroll
   for (int sgi = 0; sgi < 4; ++sgi) {
     if (sgi < p.nseg && tid == 0) {
       const AttnSeg& sg = p.seg[sgi];
-      const int kvrow = sg.kv_mod == 0 ? row : (sg.kv_mod == mod0 ? rmod0 : row % sg.kv_mod);
+      const int kvrow = sg.kv_mod == 0 ? row : (sg.kv_mod == mod0 ? rmod0 : item % sg.kv_mod);
       segtab[sgi].kb = (const char*)(sg.K + (long)kvrow * sg.k_row_stride + (long)head * sg.k_head_stride);
       segtab[sgi].vb = (const char*)(sg.Vt + (long)kvrow * sg.vt_row_stride + (long)head * sg.vt_head_stride);
       segtab[sgi].kld = (int)sg.k_ld * 2; segtab[sgi].vld = (int)sg.vt_ld * 2;
@@ -1464,6 +1470,7 @@ hipError_t launch_attention_bf16(const AttnArgs& a, hipStream_t st) {
   for (int s = 0; s < a.nseg; ++s)
     if ((a.seg[s].vt_ld & 7) || (a.seg[s].k_ld & 7) || !a.seg[s].nkeys) return hipErrorInvalidValue;
   if (a.qlen && (a.causal || a.O8 || a.prof)) return hipErrorInvalidValue;      // the length forms exist for the joint attention only
+  if (a.row_item && (a.causal || a.O8 || a.prof)) return hipErrorInvalidValue;  // so does the row map
   static std::atomic<unsigned long long> prepared[5];
   const void* ks[5] = {(const void*)attn_kernel<false, false, false>, (const void*)attn_kernel<true, false, false>,
                        (const void*)attn_kernel<false, true, false>, (const void*)attn_kernel<true, true, false>,

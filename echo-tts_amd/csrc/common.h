@@ -189,6 +189,10 @@ struct AttnArgs {
   // whose first query is at or beyond it writes zeros to its O block and 0 to its `redo` word and does no K / V work.  nullptr (every call
   // without a length table): the kernels above, unchanged.  Only for the joint attention (no causal mask, no per-key bias, no O8).
   const int* qlen;
+  // row map: row_item[row] = the batch item whose shared KV (every segment with kv_mod > 0, its per-key bias included) `row`
+  // reads: kvrow = item % kv_mod.  The self segment (kv_mod 0), nkeys, qlen, Q, O and G stay indexed by the row.  Device, [rows]; nullptr
+  // (every call without a map): item = row, the kernels' arithmetic as it was.  Not with O8 (the e4m3 output has no row-map form).
+  const int* row_item;
 };
 inline long attn_redo_words(int rows, int H, int S) { return (long)rows * H * ((S + 127) / 128); }      // enough for the 128-query block mode
 hipError_t launch_attention_bf16(const AttnArgs& a, hipStream_t st);
@@ -249,20 +253,25 @@ struct EulerArgs {
 template <typename T> hipError_t launch_euler(const EulerArgs& e, hipStream_t st);
 
 // Mixed sampler call (echo_sample_euler_items): what euler_kernel takes as launch scalars comes from a device table with one entry
-// per (step, utterance); the row layout (R, R_next) stays a property of the launch.
+// per (step, utterance), the rows of the forward that belong to the item included.
 struct EulerItem {
   int has_cfg; float s_text, s_spk;
   int rescale; float r_inv1mt, r_ratio, r_1mt;
   float dt;
   int done;                 // per-utterance step counts: the item finished at an earlier iteration (0 in a call without step counts)
+  // Rows of the forward.  row[0..2]: where THIS step's forward computed the item's conditional, text-uncond and speaker-uncond
+  // output (row[1], row[2] are read only when the item has CFG at the step).  next[0..2]: the rows of the NEXT forward that take the item's
+  // updated x_t as their input, -1 for none.  The rectangular calls fill b, B + b, 2B + b (next: as many as the next forward has), which is
+  // the addressing the kernel always had; a compacted call names the rows its plan gave the item.
+  int row[3], next[3];
 };
 // One launch of the mixed sampler's update.  init: x = x0 * init_scale for valid tokens (the table entry is not read).  step: the Euler update
 // of an item's valid tokens; an item with done != 0 keeps x as it is (no store to x at all) and only has the next forward's input staged
 // from it.  Token s of item b is padding when s >= len[b]: never read from x0, written as 0 by the init launch, 0 ever after.
 struct EulerItemsArgs {
   float* x; const void* v; long ldv; void* xin; long ld_xin;      // as EulerArgs
-  int B, S, L, R, R_next;
-  const EulerItem* items;   // device, B entries: this step's (unused by the init launch)
+  int B, S, L, R;           // R = 3: an item with has_cfg combines its three rows; 1: no item does
+  const EulerItem* items;   // device, B entries: this step's (the init launch reads `next` alone: the rows of the first forward)
   const float* init_scale;  // device, B floats (1.0f = no truncation); read by the init launch only
   const int* len;           // device, B entries, 1 <= len[b] <= S; nullptr: every token is valid
   const float* x0;          // the caller's x_init (B, S, L): read by the init launch, valid tokens only

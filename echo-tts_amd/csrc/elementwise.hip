@@ -315,12 +315,12 @@ __global__ void euler_kernel(const EulerArgs e) {
 
 // One token element of a mixed call's Euler step (CFG combine, temporal rescale, update): the ONE statement of that arithmetic.
 template <typename T>
-__device__ __forceinline__ float euler_item_update(const EulerItemsArgs& e, const EulerItem& it, const long tok, const int l, const long bs, float x) {
+__device__ __forceinline__ float euler_item_update(const EulerItemsArgs& e, const EulerItem& it, const int s, const int l, float x) {
   const T* v = (const T*)e.v;
-  float vp = Num<T>::ld(v[tok * e.ldv + l]);
+  float vp = Num<T>::ld(v[((long)it.row[0] * e.S + s) * e.ldv + l]);
   if (e.R == 3 && it.has_cfg) {
-    const float vut = Num<T>::ld(v[(bs + tok) * e.ldv + l]);
-    const float vus = Num<T>::ld(v[(2 * bs + tok) * e.ldv + l]);
+    const float vut = Num<T>::ld(v[((long)it.row[1] * e.S + s) * e.ldv + l]);
+    const float vus = Num<T>::ld(v[((long)it.row[2] * e.S + s) * e.ldv + l]);
     const float a = __fmul_rn(it.s_text, __fsub_rn(vp, vut));
     const float b = __fmul_rn(it.s_spk, __fsub_rn(vp, vus));
     vp = __fadd_rn(__fadd_rn(vp, a), b);
@@ -351,28 +351,30 @@ __global__ void euler_items_kernel(const EulerItemsArgs e) {
   const long tok = i / e.L;
   const int l = (int)(i - tok * e.L);
   const int item = (int)(tok / e.S);
-  const long bs = (long)e.B * e.S;
-  const bool valid = !e.len || (int)(tok - (long)item * e.S) < e.len[item];
+  const int s = (int)(tok - (long)item * e.S);
+  const bool valid = !e.len || s < e.len[item];
   float x = 0.0f;
   bool store = true;
+  const EulerItem it = e.items[item];
   if (e.init) {
     if (valid) {
       x = e.x0[i];
-      const float s = e.init_scale[item];
-      if (s != 1.0f) x = __fmul_rn(x, s);
+      const float sc = e.init_scale[item];
+      if (sc != 1.0f) x = __fmul_rn(x, sc);
     }
   } else {
-    const EulerItem it = e.items[item];
     if (it.done) {
       x = e.x[i];
       store = false;
     } else if (valid) {
-      x = euler_item_update<T>(e, it, tok, l, bs, e.x[i]);
+      x = euler_item_update<T>(e, it, s, l, e.x[i]);
     }
   }
   if (store) e.x[i] = x;
   T* xin = (T*)e.xin;
-  for (int r = 0; r < e.R_next; ++r) xin[(r * bs + tok) * e.ld_xin + l] = Num<T>::st(x);
+#pragma unroll
+  for (int r = 0; r < 3; ++r)
+    if (it.next[r] >= 0) xin[((long)it.next[r] * e.S + s) * e.ld_xin + l] = Num<T>::st(x);
 }
 template <typename T>
 __global__ void stage_x_len_kernel(const T* __restrict__ x, int L, T* __restrict__ xin, long ld_xin, long n, int B, int S, const int* __restrict__ len) {
@@ -795,7 +797,7 @@ template <typename T> hipError_t launch_euler(const EulerArgs& e, hipStream_t st
   return hipGetLastError();
 }
 template <typename T> hipError_t launch_euler_items(const EulerItemsArgs& e, hipStream_t st) {
-  if (!e.x || !e.xin || (e.init ? (!e.init_scale || !e.x0) : (!e.items || !e.v)) || e.B < 1 || e.S < 1 || e.L < 1) return hipErrorInvalidValue;
+  if (!e.x || !e.xin || !e.items || (e.init ? (!e.init_scale || !e.x0) : !e.v) || e.B < 1 || e.S < 1 || e.L < 1) return hipErrorInvalidValue;
   hipLaunchKernelGGL(euler_items_kernel<T>, grid1d((long)e.B * e.S * e.L), dim3(256), 0, st, e);
   return hipGetLastError();
 }

@@ -185,7 +185,7 @@ struct EngineBase {
   // item_pos / item_len (host tables of B entries, each may be null): per-utterance start positions (start_pos is then ignored) / lengths
   virtual int dit_forward(const void* x, const void* temb, int n_t, const int32_t* row_t, int rows, int B, int S, int start_pos,
                           const int32_t* item_pos, const int32_t* item_len, int use_latent, const int32_t* ton, const int32_t* son, float* v,
-                          hipStream_t st) = 0;
+                          hipStream_t st, const int32_t* row_item = nullptr /* host, rows: the rows' items */) = 0;
   virtual int sample_euler(const echo_sampler_params* p, const float* x0, float* out, hipStream_t st) = 0;
   virtual int dac_decode(const float* lat, int T, float scale, float* wav, hipStream_t st) = 0;
   virtual int dac_decode_zq(const float* z, int T, float* wav, hipStream_t st) = 0;
@@ -197,6 +197,7 @@ struct EngineBase {
   virtual int debug_get_kv(int which, int layer, float* k, float* v, int* B, int* T) = 0;
   int corrupt_countdown = 0;      // echo_debug_corrupt_tile
   bool fp8 = false;               // bf16 engine with cfg.dit_fp8, set by finalize_dit (the step-count entry point refuses it in its own words)
+  int64_t row_forwards = 0;       // echo_debug_last_row_forwards: sum of `rows` over the forwards of the last sampler call
   bool steps_ignore_done = false; // echo_debug_item_steps_ignore_done: one-shot, consumed by the next step-count call that builds its table
   virtual int voice_capture(struct VoiceSnap** out, hipStream_t st) = 0;
   virtual int voice_bind(const struct VoiceSnap* v, hipStream_t st) = 0;
@@ -209,8 +210,9 @@ struct EngineBase {
   virtual int fp8_set_static(const float* s, int n) = 0;
   // mixed batches (added under ABI 8): per-utterance sampler parameters, speaker-KV scaling and cached voices in one call
   // item_pos / item_len / item_steps (host tables of B entries, each may be null): per-utterance start positions / lengths / step counts
+  // compact: every iteration runs only the rows somebody reads, described by a row map; item_steps may then be null too
   virtual int sample_euler_items(const echo_sampler_params* p, const echo_sampler_item* items, const int32_t* item_pos, const int32_t* item_len,
-                                 const int32_t* item_steps, const float* x0, float* out, hipStream_t st) = 0;
+                                 const int32_t* item_steps, const float* x0, float* out, hipStream_t st, bool compact = false) = 0;
   virtual int scale_speaker_kv_items(const float* scales, const int32_t* max_layers, int n, hipStream_t st) = 0;
   virtual int voice_bind_items(const struct VoiceSnap* const* v, int n, hipStream_t st) = 0;
 };
@@ -305,14 +307,24 @@ struct Engine : EngineBase {
   const int* len_dev() const { return b_pos_rope.as<int>() + LEN_TAB_OFF; }
   // The per-utterance host tables of one forward / sampler call as prepare_item_tables() resolved them: both null (every item at the call's
   // start_pos with S tokens), or pos alone, or both.
-  struct ItemTables { const int32_t* pos = nullptr; const int32_t* len = nullptr; };
+  // Row map: row_item (host, rows entries) names the item whose position, length, text and speaker KV each row uses instead of
+  // r % B; the other three are the device side of ONE row set as prepare_row_set() laid it out - the map, the [4][MAXROWS] key counts (their self
+  // slot is the qlen table) and, with positions, the rows * S gathered RoPE rows.  All null: the rectangular layout.
+  struct ItemTables {
+    const int32_t* pos = nullptr; const int32_t* len = nullptr;
+    const int32_t* row_item = nullptr; const int* row_item_dev = nullptr; const int* nk_dev = nullptr; const float2* rope_rows = nullptr;
+  };
+  // what attention() / attention_f32() / add_seg_bias() read while a forward with a row map runs (forward_rows sets and clears them)
+  const int32_t* cur_row_item = nullptr; const int* cur_row_item_dev = nullptr; const int* cur_nk_dev = nullptr;
+  const int* nk_dev() const { return cur_nk_dev ? cur_nk_dev : b_nkeys.as<int>(); }
+  DevBuf b_row_sets;                // row map: the device tables of a call's row sets, ROW_SET_BYTES + rope rows each
   HostStage stage_items;
   std::vector<DevBuf*> all_bufs() {
     return {&b_kv_text, &b_vt_text, &b_kv_spk, &b_vt_spk, &b_kv_lat, &b_vt_lat, &b_nkeys, &b_bias_text, &b_bias_spk,
             &b_xin, &b_x, &b_xn, &b_qkvg, &b_vt_self, &b_attn, &b_h, &b_vout, &b_scores, &b_biasrows, &b_segmeta, &b_attn_redo,
             &b_mod, &b_c1, &b_c2, &b_cond, &b_sc, &b_dn, &b_xstate, &b_vf32,
             &b_ex, &b_exn, &b_eqkvg, &b_evt, &b_eattn, &b_eh, &b_ein, &b_enk,
-            &b_dacA, &b_dacB, &b_dacC, &b_dq, &b_dscore, &b_dvt, &b_dmisc, &b_items, &b_voice_tab, &b_pos_rope, &b_attn_keep};
+            &b_dacA, &b_dacB, &b_dacC, &b_dq, &b_dscore, &b_dvt, &b_dmisc, &b_items, &b_voice_tab, &b_pos_rope, &b_attn_keep, &b_row_sets};
   }
   // text / speaker / latent cache geometry
   int kvB = 0;          // batch size of the text cache (= utterances per sampler call)
@@ -706,7 +718,7 @@ struct Engine : EngineBase {
   int attention(const T* q, long q_ld, const T* gate, long g_ld, T* out, long o_ld, int rows, int S, int H, const SegDesc* segs,
                 int nseg, bool causal, hipStream_t st, uint8_t* out8 = nullptr, long o8_ld = 0, float o8_inv = 0.f, int g_act = 0,
                 const int* qlen = nullptr /* bf16: per-row query counts (AttnArgs.qlen), the joint attention of a length call */) {
-    const int* nk = b_nkeys.as<int>();
+    const int* nk = nk_dev();
     if constexpr (Num<T>::is_bf16) {
       AttnArgs a;
       memset(&a, 0, sizeof(a));
@@ -730,7 +742,8 @@ struct Engine : EngineBase {
       if (n == 0) return fail("attention without keys");
       CK(b_attn_redo.reserve((size_t)attn_redo_words(rows, H, S) * sizeof(int)));
       a.redo = b_attn_redo.as<int>();
-      a.qlen = qlen;
+      a.qlen = qlen; a.row_item = cur_row_item_dev;
+      if (cur_row_item_dev && (causal || out8)) return fail("row map: the attention has no causal / e4m3 form under a row map");
       if (profiling) {
         if (attn_events_used == attn_events.size()) {
           hipEvent_t e0, e1;
@@ -750,6 +763,20 @@ struct Engine : EngineBase {
     }
   }
 
+  // The batched score / PV GEMMs of attention_f32 run once per run of query rows [r0, r0 + nr) whose KV rows are consecutive, kv0 .. kv0 + nr - 1
+  // (shared1, kv_mod == 1: one run, batch stride 0).  Without a row map these are the blocks of kv_mod rows the code always formed (the self
+  // segment: one run); with one a run ends where the next row's item is not the successor.  The rectangular map gives the same runs.
+  struct KvRun { int r0, nr, kv0; };
+  std::vector<KvRun> kv_runs(int rows, int kv_mod) const {
+    std::vector<KvRun> runs;
+    if (kv_mod <= 1) { runs.push_back(KvRun{0, rows, 0}); return runs; }
+    for (int r = 0; r < rows; ++r) {
+      const int kv = (cur_row_item ? cur_row_item[r] : r) % kv_mod;
+      if (!runs.empty() && kv != 0 && kv == runs.back().kv0 + runs.back().nr) ++runs.back().nr;
+      else runs.push_back(KvRun{r, 1, kv});
+    }
+    return runs;
+  }
   // unfused exact-fp32 attention for parity mode: scores GEMM -> softmax -> PV GEMM
   int attention_f32(const T* q, long q_ld, const T* gate, long g_ld, T* out, long o_ld, int rows, int S, int H, const SegDesc* segs,
                     int nseg, bool causal, hipStream_t st) {
@@ -772,7 +799,7 @@ struct Engine : EngineBase {
       CK(hipMemcpyAsync(b_segmeta.p, hmeta, sizeof(hmeta), hipMemcpyHostToDevice, st));
       int* nk_act = b_segmeta.as<int>() + 8;
       for (int i = 0; i < n; ++i)
-        CK(hipMemcpyAsync(nk_act + i * MAXROWS, b_nkeys.as<int>() + slot[i] * MAXROWS, sizeof(int) * MAXROWS, hipMemcpyDeviceToDevice, st));
+        CK(hipMemcpyAsync(nk_act + i * MAXROWS, nk_dev() + slot[i] * MAXROWS, sizeof(int) * MAXROWS, hipMemcpyDeviceToDevice, st));
       CK(hipStreamSynchronize(st));  // hmeta is a stack array (parity mode only)
       const float *b2 = nullptr, *b3 = nullptr; long b2s = 0, b3s = 0; int b2m = 0, b3m = 0;
       // slots 2/3 of build_bias_kernel refer to ACTIVE segment indices here; map text/speaker biases accordingly
@@ -793,11 +820,10 @@ struct Engine : EngineBase {
       for (int i = 0; i < n; ++i) {
         const SegDesc& sg = *act[i];
         const bool shared1 = sg.kv_mod == 1;      // one kv row shared by every query row: a single group with batch stride 0
-        const int groups = shared1 ? 1 : sg.kv_mod ? (rows + sg.kv_mod - 1) / sg.kv_mod : 1;
-        const int per = shared1 ? rows : sg.kv_mod ? sg.kv_mod : rows;
-        for (int gidx = 0; gidx < groups; ++gidx) {
-          const int r0 = gidx * per, nr = std::min(per, rows - r0);
-          GemmArgs g = G(q + (long)r0 * S * q_ld, q_ld, sg.K + (sg.kv_mod ? 0 : (long)r0 * sg.k_row_stride), sg.k_ld,
+        const std::vector<KvRun> runs = kv_runs(rows, sg.kv_mod);
+        for (const KvRun& kr : runs) {
+          const int r0 = kr.r0, nr = kr.nr;
+          GemmArgs g = G(q + (long)r0 * S * q_ld, q_ld, sg.K + (long)kr.kv0 * sg.k_row_stride, sg.k_ld,
                          (T*)(sc + (long)r0 * H * S * ld + off[i]), ld, S, wdt[i], 128);
           g.nbatch = nr * H; g.nbi = H;
           g.a_bo = (long)S * q_ld; g.a_bi = 128;
@@ -811,12 +837,11 @@ struct Engine : EngineBase {
       for (int i = 0; i < n; ++i) {
         const SegDesc& sg = *act[i];
         const bool shared1 = sg.kv_mod == 1;
-        const int groups = shared1 ? 1 : sg.kv_mod ? (rows + sg.kv_mod - 1) / sg.kv_mod : 1;
-        const int per = shared1 ? rows : sg.kv_mod ? sg.kv_mod : rows;
-        for (int gidx = 0; gidx < groups; ++gidx) {
-          const int r0 = gidx * per, nr = std::min(per, rows - r0);
+        const std::vector<KvRun> runs = kv_runs(rows, sg.kv_mod);
+        for (const KvRun& kr : runs) {
+          const int r0 = kr.r0, nr = kr.nr;
           T* o = out + (long)r0 * S * o_ld;
-          GemmArgs g = G((const T*)(sc + (long)r0 * H * S * ld + off[i]), ld, sg.Vt + (sg.kv_mod ? 0 : (long)r0 * sg.vt_row_stride),
+          GemmArgs g = G((const T*)(sc + (long)r0 * H * S * ld + off[i]), ld, sg.Vt + (long)kr.kv0 * sg.vt_row_stride,
                          sg.vt_ld, o, o_ld, S, 128, wdt[i]);
           g.nbatch = nr * H; g.nbi = H;
           g.a_bo = (long)H * S * ld; g.a_bi = (long)S * ld;
@@ -1247,8 +1272,8 @@ struct Engine : EngineBase {
   // tabs.len (nullptr: every item has S tokens): the self segment of row r ends at item r % B's own length
   void set_row_keys(int rows, int B, int S, int start_pos, bool use_latent, const int32_t* ton, const int32_t* son, const ItemTables& tabs) {
     for (int r = 0; r < MAXROWS; ++r) {
-      const int b = B > 0 ? r % B : 0;
       const bool in = r < rows;
+      const int b = tabs.row_item ? (in ? tabs.row_item[r] : 0) : B > 0 ? r % B : 0;      // row map: the row's item
       host_nk[0 * MAXROWS + r] = in ? (tabs.len ? tabs.len[b] : S) : 0;
       int nl = 0;
       const int sp = tabs.pos ? tabs.pos[b] : start_pos;
@@ -1273,7 +1298,12 @@ struct Engine : EngineBase {
   int forward_rows(int rows, int B, int S, int start_pos, bool use_latent, const T* modrow, hipStream_t st, const std::vector<ModSeg>* segs_in,
                    const ItemTables& tabs) {
     const bool item_pos = tabs.pos != nullptr;
-    const int* const qlen = tabs.len && Num<T>::is_bf16 ? b_nkeys.as<int>() : nullptr;
+    struct RowScope {      // the row map's device tables are what the attention dispatch reads for the duration of this forward
+      Engine* e;
+      RowScope(Engine* e_, const ItemTables& t) : e(e_) { e->cur_row_item = t.row_item; e->cur_row_item_dev = t.row_item_dev; e->cur_nk_dev = t.nk_dev; }
+      ~RowScope() { e->cur_row_item = nullptr; e->cur_row_item_dev = nullptr; e->cur_nk_dev = nullptr; }
+    } row_scope(this, tabs);
+    const int* const qlen = tabs.len && Num<T>::is_bf16 ? nk_dev() : nullptr;
     const std::vector<ModSeg> one = {ModSeg{0, rows, modrow}};
     const std::vector<ModSeg>& segs = segs_in ? *segs_in : one;
     const int D = cfg.model_size, L = cfg.num_layers, H = cfg.num_heads, F = cfg.intermediate_size, M = rows * S;
@@ -1281,8 +1311,9 @@ struct Engine : EngineBase {
     T *xin = b_xin.as<T>(), *x = b_x.as<T>(), *xn = b_xn.as<T>(), *qkvg = b_qkvg.as<T>(), *vts = b_vt_self.as<T>(),
       *ao = b_attn.as<T>(), *hh = b_h.as<T>(), *vout = b_vout.as<T>();
     if (!item_pos && start_pos + S > rope_npos) return fail("rope table too short");
-    const float2* const rope_rows = item_pos ? (const float2*)((const char*)b_pos_rope.p + POS_TAB_BYTES) : rope;
-    const int rope_pos0 = item_pos ? 0 : start_pos, rope_mod = item_pos ? B * S : S;
+    // (row map: the gather is per ROW, rows * S entries, so the consumers' m % modulus is again the token's own row of the table)
+    const float2* const rope_rows = !item_pos ? rope : tabs.row_item ? tabs.rope_rows : (const float2*)((const char*)b_pos_rope.p + POS_TAB_BYTES);
+    const int rope_pos0 = item_pos ? 0 : start_pos, rope_mod = !item_pos ? S : tabs.row_item ? rows * S : B * S;
     {
       GemmArgs g = G(xin, lat_pad, in_w, lat_pad, x, D, M, D, lat_pad);
       g.bias = in_b;
@@ -1473,8 +1504,11 @@ struct Engine : EngineBase {
   // is what has to fit the table.  Once per call, in front of the step loop; no allocation and no synchronisation once the geometry is warm.
   // Nothing is queued when a table is refused.  A refusal speaks of the tables the caller gave, and what only the length forms cannot do
   // (the fp8 engine, a key mask that is not a prefix) is refused only for a length table.
-  int prepare_item_tables(const int32_t* item_pos, const int32_t* item_len, int fallback_pos, int B, int S, int32_t* pos_out, hipStream_t st) {
-    const std::string what = item_len ? "per-utterance lengths: " : "per-utterance start positions: ";
+  // rows_call (a call with a row map): the same checks in that call's name and nothing queued here - its tables and its gather
+  // are per ROW (prepare_row_set).
+  int prepare_item_tables(const int32_t* item_pos, const int32_t* item_len, int fallback_pos, int B, int S, int32_t* pos_out, hipStream_t st,
+                          bool rows_call = false) {
+    const std::string what = rows_call ? "row map: " : item_len ? "per-utterance lengths: " : "per-utterance start positions: ";
     if (item_len && fp8) return fail(what + "not supported by the fp8 engine (dit_fp8): its e4m3 attention output has no length form; use the bf16 engine");
     static_assert((LEN_TAB_OFF + ECHO_MAX_ITEMS) * sizeof(int32_t) <= POS_TAB_BYTES && ECHO_MAX_ITEMS <= LEN_TAB_OFF && 3 * ECHO_MAX_ITEMS == MAXROWS, "table layout");
     if (B < 1 || B > ECHO_MAX_ITEMS) return fail(what + "at most 32 items per call (3 B <= 96 rows)");
@@ -1493,10 +1527,31 @@ struct Engine : EngineBase {
         return fail(what + (item_len ? "a start position plus its length" : "a start position plus S") + " runs past the rope table (rope table too short)");
       tab[b] = pos_out[b] = sp; tab[LEN_TAB_OFF + b] = n;
     }
+    if (rows_call) return ECHO_OK;
     CK(b_pos_rope.reserve(POS_TAB_BYTES + (size_t)B * S * 64 * sizeof(float2)));
     CK(stage_items.push(tab, POS_TAB_BYTES, b_pos_rope.p, st));
     CK(launch_rope_gather(rope, b_pos_rope.as<int>(), len_dev(), (float2*)((char*)b_pos_rope.p + POS_TAB_BYTES), B, S, st));
     return ECHO_OK;
+  }
+  // One row set of a call with a row map as the device sees it: ROW_SET_BYTES of int32 - the map, then the start position and the
+  // length of every row (its item's), then the [4][MAXROWS] key counts - followed, where the call has positions, by the rows * S RoPE rows
+  // gathered for exactly these rows.  fill_row_set() writes the host image after set_row_keys() has described the set; row_set_view() names the
+  // device copy at `base`.  launch_rope_gather, launch_stage_x_len and launch_convert_to_f32_len take the per-row tables with B = rows.
+  static constexpr size_t ROW_SET_BYTES = 3072;
+  static_assert(7 * MAXROWS * sizeof(int32_t) <= ROW_SET_BYTES && ROW_SET_BYTES % 16 == 0, "row set layout");
+  void fill_row_set(int32_t* dst, int rows, int S, const ItemTables& tabs) const {
+    memset(dst, 0, ROW_SET_BYTES);
+    for (int r = 0; r < rows; ++r) {
+      const int b = tabs.row_item[r];
+      dst[r] = b; dst[MAXROWS + r] = tabs.pos ? tabs.pos[b] : 0; dst[2 * MAXROWS + r] = tabs.len ? tabs.len[b] : S;
+    }
+    memcpy(dst + 3 * MAXROWS, host_nk.data(), 4 * MAXROWS * sizeof(int32_t));
+  }
+  static const int* row_set_pos(const int* base) { return base + MAXROWS; }
+  static const int* row_set_len(const int* base) { return base + 2 * MAXROWS; }
+  static ItemTables row_set_view(ItemTables t, const int* base, const float2* rope_rows) {
+    t.row_item_dev = base; t.nk_dev = base + 3 * MAXROWS; t.rope_rows = rope_rows;
+    return t;
   }
   // V^T of the self segment is [rows][D][rup(S, 64)]; the QKV tails write columns < S, and the attention's last key tile reads all 64 of its
   // columns (masked keys meet a zero probability).  Columns [S, rup(S, 64)) hold whatever a call of another geometry left there: a length call
@@ -1508,14 +1563,23 @@ struct Engine : EngineBase {
     return ECHO_OK;
   }
   // temb: (n_t, E) timestep embeddings; row_t (host, rows) = which of them each row uses (nullptr: all rows use embedding 0)
+  // row_item (host, rows entries; nullptr: row r belongs to item r % B): the forward's rows are described by a map
   int dit_forward(const void* x, const void* temb, int n_t, const int32_t* row_t, int rows, int B, int S, int start_pos, const int32_t* item_pos,
-                  const int32_t* item_len, int use_latent, const int32_t* ton, const int32_t* son, float* v, hipStream_t st) override {
+                  const int32_t* item_len, int use_latent, const int32_t* ton, const int32_t* son, float* v, hipStream_t st,
+                  const int32_t* row_item = nullptr) override {
     if (!dit_ready) return fail("echo_finalize_dit was not called");
-    if (rows < 1 || rows > MAXROWS || B < 1 || rows % B || B != kvB) return fail("bad rows/B");
+    if (row_item) {
+      if (fp8) return fail("row map: not supported by the fp8 engine (dit_fp8): its e4m3 attention output has no row-map form; use the bf16 engine");
+      if (rows < 1 || rows > MAXROWS) return fail("row map: 1 <= rows <= 96");
+      if (B < 1 || B > ECHO_MAX_ITEMS || B != kvB) return fail("row map: B must be the batch size of the text cache (at most 32 items)");
+      for (int r = 0; r < rows; ++r)
+        if (row_item[r] < 0 || row_item[r] >= B) return fail("row map: a row_item entry is out of range (0 <= row_item[r] < B)");
+    } else if (rows < 1 || rows > MAXROWS || B < 1 || rows % B || B != kvB) return fail("bad rows/B");
     int32_t pos[ECHO_MAX_ITEMS];
     ItemTables tabs;
+    tabs.row_item = row_item;
     if (item_pos || item_len) {
-      CKI(prepare_item_tables(item_pos, item_len, start_pos, B, S, pos, st));
+      CKI(prepare_item_tables(item_pos, item_len, start_pos, B, S, pos, st, row_item != nullptr));
       tabs.pos = pos; tabs.len = item_len;
     }
     if (spk_T > 0 && (spkB < 1 || kvB % spkB)) return fail("the speaker cache's batch size must divide the text cache's");
@@ -1533,16 +1597,28 @@ struct Engine : EngineBase {
       else segs.push_back(ModSeg{r, 1, mod});
     }
     set_row_keys(rows, B, S, start_pos, use_latent != 0, ton, son, tabs);
-    CKI(push_nkeys(st));
+    int lenB = B;                        // the length table's modulus and the table: per item, or per row under a map
+    const int* lens = len_dev();
+    if (row_item) {
+      CK(b_row_sets.reserve(ROW_SET_BYTES + (size_t)rows * S * 64 * sizeof(float2)));
+      int32_t blk[ROW_SET_BYTES / sizeof(int32_t)];
+      fill_row_set(blk, rows, S, tabs);
+      CK(stage_items.push(blk, ROW_SET_BYTES, b_row_sets.p, st));
+      const int* base = b_row_sets.as<int>();
+      float2* rr = (float2*)((char*)b_row_sets.p + ROW_SET_BYTES);
+      if (tabs.pos) CK(launch_rope_gather(rope, row_set_pos(base), row_set_len(base), rr, rows, S, st));
+      tabs = row_set_view(tabs, base, rr);
+      lenB = rows; lens = row_set_len(base);
+    } else CKI(push_nkeys(st));
     // x (M, latent) -> xin (M, lat_pad) zero padded.  With lengths the caller's padding tokens are not read: zeros take their place, and zeros leave in v
     if (tabs.len) {
-      CK(launch_stage_x_len<T>((const T*)x, cfg.latent_size, b_xin.as<T>(), lat_pad, rows, B, S, len_dev(), st));
+      CK(launch_stage_x_len<T>((const T*)x, cfg.latent_size, b_xin.as<T>(), lat_pad, rows, lenB, S, lens, st));
       CKI(clear_vt_tail(rows, S, st));
     } else {
       CK(hipMemcpy2DAsync(b_xin.p, lat_pad * sizeof(T), x, cfg.latent_size * sizeof(T), cfg.latent_size * sizeof(T), M, hipMemcpyDeviceToDevice, st));
     }
     CKI(forward_rows(rows, B, S, start_pos, use_latent != 0, b_mod.as<T>(), st, &segs, tabs));
-    if (tabs.len) CK(launch_convert_to_f32_len<T>(b_vout.as<T>(), 128, v, cfg.latent_size, rows, B, S, cfg.latent_size, len_dev(), st));
+    if (tabs.len) CK(launch_convert_to_f32_len<T>(b_vout.as<T>(), 128, v, cfg.latent_size, rows, lenB, S, cfg.latent_size, lens, st));
     else CK(launch_convert_to_f32<T>(b_vout.as<T>(), 128, v, cfg.latent_size, M, cfg.latent_size, st));
     return ECHO_OK;
   }
@@ -1591,11 +1667,13 @@ struct Engine : EngineBase {
     e.x = xs; e.v = b_vout.p; e.ldv = 128; e.xin = b_xin.p; e.ld_xin = lat_pad;
     e.B = B; e.S = S; e.L = Lz; e.R = 1;
     e.R_next = p->steps[0].has_cfg ? 3 : 1;
+    row_forwards = 0;
     e.init = 1; e.init_scale = p->has_truncation ? p->init_scale : 1.0f;   // x_t = x_t * truncation_factor (inference.py:478-479) only when one was given; 0.0 is then honoured
     CK(launch_euler<T>(e, st));
     for (int i = 0; i < N; ++i) {
       const echo_step& sp = p->steps[i];
       const int rows = sp.has_cfg ? rows3 : B;
+      row_forwards += rows;
       CKI(forward_rows(rows, B, S, p->start_pos, p->use_latent != 0, b_mod.as<T>() + (long)i * modstride, st, nullptr, ItemTables{}));
       if (sp.kv_unscale_after) CKI(scale_speaker_kv(1.0f / p->kv_scale, p->kv_max_layers, st));
       e.init = 0;
@@ -1622,8 +1700,44 @@ struct Engine : EngineBase {
   // orders the items so that groups are contiguous: at most 3 G segments - and a finished item's rows use the modulation of its group's last step, so
   // that everything they leave in the workspace stays finite.  Its table entries carry `done`: euler_items_kernel leaves its x_t alone.
   static constexpr int MAX_STEP_GROUPS = 8;
+  // Compacted row sets.  Iteration i runs exactly the rows somebody reads: the conditional row of every ACTIVE item, and the
+  // text-uncond and speaker-uncond rows of the active items that have CFG at their own step i.  Order: group-major (groups in order of first
+  // appearance; a finished group has no rows), inside a group the conditional rows, then the text-uncond, then the speaker-uncond rows, items in
+  // call order - one modulation segment per active group, and with one group and every item in CFG the 3 B layout of the rectangular calls.
+  // Writes row[] of every step entry and next[] of the entry before it (tab[-B ..] is the init launch's), dedups the sets (a set changes only
+  // where a CFG window opens or closes or a group finishes) and names each iteration's.
+  struct RowSet { int rows = 0; std::vector<int32_t> item, ton, son; std::vector<int> host_nk; };
+  int plan_row_sets(int B, int N, int G, const std::vector<int>& grp, const std::vector<int>& grp_steps, const int32_t* item_steps, EulerItem* tab,
+                    std::vector<RowSet>& sets, std::vector<int>& set_of) {
+    for (int i = -1; i < N; ++i)
+      for (int b = 0; b < B; ++b) { EulerItem& t = tab[(long)i * B + b]; t.next[0] = t.next[1] = t.next[2] = -1; }
+    for (int i = 0; i < N; ++i) {
+      RowSet rs;
+      for (int g = 0; g < G; ++g) {
+        if (item_steps && i >= grp_steps[g]) continue;
+        for (int kind = 0; kind < 3; ++kind)
+          for (int b = 0; b < B; ++b) {
+            EulerItem& t = tab[(long)i * B + b];
+            if (grp[b] != g || (kind > 0 && !t.has_cfg)) continue;
+            t.row[kind] = tab[(long)(i - 1) * B + b].next[kind] = rs.rows++;
+            rs.item.push_back(b); rs.ton.push_back(kind != 1); rs.son.push_back(kind != 2);
+          }
+      }
+      for (int b = 0; b < B; ++b) {      // rows an entry does not have are never read; name none
+        EulerItem& t = tab[(long)i * B + b];
+        if (t.done || !t.has_cfg) t.row[1] = t.row[2] = -1;
+        if (t.done) t.row[0] = -1;
+      }
+      if (rs.rows > MAXROWS) return fail("compacted row set: more than 96 rows");
+      size_t k = 0;
+      while (k < sets.size() && !(sets[k].item == rs.item && sets[k].ton == rs.ton && sets[k].son == rs.son)) ++k;
+      if (k == sets.size()) sets.push_back(std::move(rs));
+      set_of[i] = (int)k;
+    }
+    return ECHO_OK;
+  }
   int sample_euler_items(const echo_sampler_params* p, const echo_sampler_item* items, const int32_t* item_pos, const int32_t* item_len,
-                         const int32_t* item_steps, const float* x0, float* out, hipStream_t st) override {
+                         const int32_t* item_steps, const float* x0, float* out, hipStream_t st, bool compact = false) override {
     if (!dit_ready) return fail("echo_finalize_dit was not called");
     if (!p || !items) return fail("mixed sampler call: null params / items");
     const int B = p->B, S = p->S, N = p->num_steps, Lz = cfg.latent_size;
@@ -1657,7 +1771,8 @@ struct Engine : EngineBase {
     const int G = item_steps ? (int)grp_steps.size() : 1;
     // host side of the step loop, prepared up front: row sets, the (step, item) table, the speaker-KV un-scaling per voice slot
     std::vector<char> any_cfg(N, 0);
-    std::vector<EulerItem> tab((size_t)N * B);
+    std::vector<EulerItem> tab_all((size_t)(N + 1) * B);      // [0]: the init launch's entries (`next` alone is read), [1 + i]: step i's
+    EulerItem* const tab = tab_all.data() + B;
     std::vector<float> init(B);
     std::vector<KvItemScales> unscale(N);
     std::vector<char> has_unscale(N, 0);
@@ -1672,7 +1787,8 @@ struct Engine : EngineBase {
         EulerItem& t = tab[(size_t)i * B + b];
         t.has_cfg = sp.has_cfg ? 1 : 0; t.s_text = items[b].cfg_scale_text; t.s_spk = items[b].cfg_scale_speaker;
         t.rescale = sp.rescale; t.r_inv1mt = sp.r_inv1mt; t.r_ratio = sp.r_ratio; t.r_1mt = sp.r_1mt; t.dt = sp.dt;
-        t.done = active || steps_ignore_done ? 0 : 1;
+        t.done = active || (steps_ignore_done && !compact) ? 0 : 1;
+        t.row[0] = b; t.row[1] = B + b; t.row[2] = 2 * B + b;
         if (sp.has_cfg && active) any_cfg[i] = 1;
         us[b] = 1.0f; ul[b] = items[b].kv_max_layers;
         if (active && sp.kv_unscale_after && spk_T > 0) {
@@ -1699,36 +1815,90 @@ struct Engine : EngineBase {
     const int rows3 = 3 * B;
     CKI(reserve_dit_ws(rows3 * S, rows3, S));
     CK(b_xstate.reserve((size_t)B * S * Lz * sizeof(float)));
-    const size_t tab_bytes = tab.size() * sizeof(EulerItem), init_bytes = (size_t)B * sizeof(float);
-    CK(b_items.reserve(tab_bytes + init_bytes));
+    // the rows of the NEXT forward that take an item's x_t (entry 0: of the first forward).  Rectangular: all B or 3 B rows, finished items included
+    // (their rows are computed and must stay finite).  Compacted: the rows plan_row_sets() gave the item, none for a finished one.
+    std::vector<RowSet> sets;          // compact: the call's distinct row sets
+    std::vector<int> set_of(N, 0);     // compact: iteration -> its set
+    if (compact) CKI(plan_row_sets(B, N, G, grp, grp_steps, item_steps, tab, sets, set_of));
+    else
+      for (int i = 0; i <= N; ++i)
+        for (int b = 0; b < B; ++b) {
+          const bool three = i < N && any_cfg[i];
+          EulerItem& t = tab_all[(size_t)i * B + b];
+          t.next[0] = i < N ? b : -1; t.next[1] = three ? B + b : -1; t.next[2] = three ? 2 * B + b : -1;
+        }
+    const size_t tab_bytes = tab_all.size() * sizeof(EulerItem), init_bytes = (size_t)B * sizeof(float);
+    const size_t sets_off = (size_t)rup((long)(tab_bytes + init_bytes), 16), sets_bytes = sets.size() * ROW_SET_BYTES;
+    CK(b_items.reserve(sets_off + sets_bytes));
     float* xs = b_xstate.as<float>();
     CKI(prof_begin(st));
-    {   // one copy: [N][B] step entries, then the B init scales
-      std::vector<char> blob(tab_bytes + init_bytes);
-      memcpy(blob.data(), tab.data(), tab_bytes);
+    {   // one copy: [1 + N][B] step entries, then the B init scales, then (compact) the tables of every row set
+      std::vector<char> blob(sets_off + sets_bytes);
+      memcpy(blob.data(), tab_all.data(), tab_bytes);
       memcpy(blob.data() + tab_bytes, init.data(), init_bytes);
+      for (size_t k = 0; k < sets.size(); ++k) {
+        RowSet& rs = sets[k];
+        ItemTables t = tabs;
+        t.row_item = rs.item.data();
+        set_row_keys(rs.rows, B, S, p->start_pos, p->use_latent != 0, rs.ton.data(), rs.son.data(), t);
+        rs.host_nk = host_nk;
+        fill_row_set((int32_t*)(blob.data() + sets_off + k * ROW_SET_BYTES), rs.rows, S, t);
+      }
       CK(stage_items.push(blob.data(), blob.size(), b_items.p, st));
     }
-    const EulerItem* tab_dev = b_items.as<EulerItem>();
+    const EulerItem* tab_dev = b_items.as<EulerItem>() + B;
+    if (compact && tabs.pos) {      // the RoPE rows of every set, gathered per row in front of the loop
+      const size_t per = (size_t)rows3 * S * 64 * sizeof(float2);
+      CK(b_row_sets.reserve(sets.size() * per));
+      for (size_t k = 0; k < sets.size(); ++k) {
+        const int* base = (const int*)((const char*)b_items.p + sets_off + k * ROW_SET_BYTES);
+        CK(launch_rope_gather(rope, row_set_pos(base), row_set_len(base), (float2*)((char*)b_row_sets.p + k * per), sets[k].rows, S, st));
+      }
+    }
     if (tabs.len) CKI(clear_vt_tail(rows3, S, st));
     CKI(compute_mod((const T*)p->temb, N * G, st));
     if (profiling) CK(hipEventRecord(ev[1], st));
     std::vector<int32_t> ton(rows3, 1), son(rows3, 1);
     for (int b = 0; b < B; ++b) { ton[B + b] = 0; son[2 * B + b] = 0; }
-    set_row_keys(rows3, B, S, p->start_pos, p->use_latent != 0, ton.data(), son.data(), tabs);
-    CKI(push_nkeys(st));
+    if (!compact) {
+      set_row_keys(rows3, B, S, p->start_pos, p->use_latent != 0, ton.data(), son.data(), tabs);
+      CKI(push_nkeys(st));
+    }
+    row_forwards = 0;
     const long modstride = (long)2 * cfg.num_layers * 3 * cfg.model_size;
     EulerItemsArgs e;
     memset(&e, 0, sizeof(e));
     e.x = xs; e.v = b_vout.p; e.ldv = 128; e.xin = b_xin.p; e.ld_xin = lat_pad;
     e.B = B; e.S = S; e.L = Lz; e.R = 1;
-    e.R_next = any_cfg[0] ? 3 : 1;
-    e.init = 1; e.init_scale = (const float*)((const char*)b_items.p + tab_bytes); e.items = tab_dev;
+    e.init = 1; e.init_scale = (const float*)((const char*)b_items.p + tab_bytes); e.items = tab_dev - B;
     e.x0 = x0; e.len = tabs.len ? len_dev() : nullptr;      // the init launch reads the caller's x_init itself and writes every x_t
     CK(launch_euler_items<T>(e, st));
     std::vector<ModSeg> segs;
     for (int i = 0; i < N; ++i) {
+      if (compact) {        // this iteration's row set: its key counts on the host side, its device tables, one modulation segment per active group
+        const RowSet& rs = sets[set_of[i]];
+        if (rs.rows == 0) continue;      // (no item runs the call's num_steps: nothing is left to compute)
+        host_nk = rs.host_nk;
+        const int* base = (const int*)((const char*)b_items.p + sets_off + (size_t)set_of[i] * ROW_SET_BYTES);
+        ItemTables t = tabs;
+        t.row_item = rs.item.data();
+        t = row_set_view(t, base, tabs.pos ? (const float2*)((const char*)b_row_sets.p + (size_t)set_of[i] * rows3 * S * 64 * sizeof(float2)) : nullptr);
+        segs.clear();
+        for (int r = 0; r < rs.rows; ++r) {
+          const T* mod = b_mod.as<T>() + ((long)i * G + grp[rs.item[r]]) * modstride;
+          if (!segs.empty() && segs.back().mod == mod) ++segs.back().nrows;
+          else segs.push_back(ModSeg{r, 1, mod});
+        }
+        CKI(forward_rows(rs.rows, B, S, p->start_pos, p->use_latent != 0, nullptr, st, &segs, t));
+        row_forwards += rs.rows;
+        if (has_unscale[i]) CKI(launch_kv_slot_scales(unscale[i], st));
+        e.init = 0; e.R = 3;      // an item with CFG at its step combines the three rows its entry names
+        e.items = tab_dev + (size_t)i * B;
+        CK(launch_euler_items<T>(e, st));
+        continue;
+      }
       const int rows = any_cfg[i] ? rows3 : B;
+      row_forwards += rows;
       if (item_steps) {     // row r takes the table of (its group, its own step i - the last one once it is finished)
         segs.clear();
         for (int r = 0; r < rows; ++r) {
@@ -1742,7 +1912,6 @@ struct Engine : EngineBase {
       if (has_unscale[i]) CKI(launch_kv_slot_scales(unscale[i], st));
       e.init = 0;
       e.R = any_cfg[i] ? 3 : 1;
-      e.R_next = (i + 1 < N && any_cfg[i + 1]) ? 3 : 1;
       e.items = tab_dev + (size_t)i * B;
       CK(launch_euler_items<T>(e, st));
     }
@@ -2662,17 +2831,17 @@ struct Engine : EngineBase {
 };
 
 __global__ void add_seg_bias_kernel(float* __restrict__ dst, long ld, int rows, int off, int w, const float* __restrict__ bias, long bias_ld,
-                                    int kv_mod) {
+                                    int kv_mod, const int* __restrict__ row_item) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= (long)rows * w) return;
   const int r = (int)(i / w), k = (int)(i - (long)r * w);
-  const int kr = kv_mod ? r % kv_mod : r;
+  const int kr = kv_mod ? (row_item ? row_item[r] : r) % kv_mod : r;      // row map: the bias of the row's item
   dst[(long)r * ld + off + k] += bias[(long)kr * bias_ld + k];
 }
 template <typename T>
 int Engine<T>::add_seg_bias(float* biasrows, long ld, int rows, int off, int w, const float* bias, long bias_ld, int kv_mod, hipStream_t st) {
   hipLaunchKernelGGL(add_seg_bias_kernel, dim3((unsigned)(((long)rows * w + 255) / 256)), dim3(256), 0, st, biasrows, ld, rows, off, w,
-                     bias, bias_ld, kv_mod);
+                     bias, bias_ld, kv_mod, cur_row_item_dev);
   CK(hipGetLastError());
   return ECHO_OK;
 }
@@ -2833,6 +3002,7 @@ int echo_voice_bind_items(echo_ctx* ctx, const echo_voice* const* voices, int n,
 static const char* const POS_CALL = "per-utterance start positions: ";
 static const char* const LEN_CALL = "per-utterance lengths: ";
 static const char* const STEPS_CALL = "per-utterance step counts: ";
+static const char* const ROWS_CALL = "row map: ";
 static int too_many_items(EngineBase* e, const char* call) { return e->fail(std::string(call) + "at most 32 items per call (3 B <= 96 rows)"); }
 static bool items_in_range(int B) { return B >= 1 && B <= ECHO_MAX_ITEMS; }
 
@@ -2854,6 +3024,16 @@ int echo_dit_forward_len(echo_ctx* ctx, const void* x, const void* temb, int n_t
   if (!item_len) return e->fail(std::string(LEN_CALL) + "null length table");
   if (!items_in_range(B)) return too_many_items(e, LEN_CALL);
   return e->dit_forward(x, temb, n_t, row_t, rows, B, S, 0, item_start_pos, item_len, use_latent, ton, son, v_out, (hipStream_t)stream);
+}
+// Row map: any 1..96 rows, each naming the item whose position, length, text and speaker KV it uses.
+int echo_dit_forward_rows(echo_ctx* ctx, const void* x, const void* temb, int n_t, const int32_t* row_t, int rows, int B, int S,
+                          const int32_t* row_item, const int32_t* item_start_pos, const int32_t* item_len, int use_latent, const int32_t* ton,
+                          const int32_t* son, float* v_out, void* stream) {
+  if (!ctx) return ECHO_ERR;
+  EngineBase* e = ctx->eng.get();
+  if (!e->dit_ready) return e->fail("echo_finalize_dit was not called");
+  if (!row_item) return e->fail(std::string(ROWS_CALL) + "null row_item table");
+  return e->dit_forward(x, temb, n_t, row_t, rows, B, S, 0, item_start_pos, item_len, use_latent, ton, son, v_out, (hipStream_t)stream, row_item);
 }
 int echo_sample_euler_items(echo_ctx* ctx, const echo_sampler_params* p, const echo_sampler_item* items, const float* x_init, float* latent_out,
                             void* stream) {
@@ -2885,6 +3065,16 @@ int echo_sample_euler_items_steps(echo_ctx* ctx, const echo_sampler_params* p, c
   if (p && !items_in_range(p->B)) return too_many_items(e, STEPS_CALL);
   return e->sample_euler_items(p, items, item_start_pos, item_len, item_steps, x_init, latent_out, (hipStream_t)stream);
 }
+// Compacted row set: the step-count call with only the rows somebody reads in every iteration; item_steps may be NULL.
+int echo_sample_euler_items_compact(echo_ctx* ctx, const echo_sampler_params* p, const echo_sampler_item* items, const int32_t* item_steps,
+                                    const int32_t* item_start_pos, const int32_t* item_len, const float* x_init, float* latent_out, void* stream) {
+  if (!ctx) return ECHO_ERR;
+  EngineBase* e = ctx->eng.get();
+  if (e->fp8) return e->fail(std::string(ROWS_CALL) + "not supported by the fp8 engine (dit_fp8): its e4m3 attention output has no row-map form; use the bf16 engine");
+  if (p && !items_in_range(p->B)) return too_many_items(e, ROWS_CALL);
+  return e->sample_euler_items(p, items, item_start_pos, item_len, item_steps, x_init, latent_out, (hipStream_t)stream, true);
+}
+int64_t echo_debug_last_row_forwards(echo_ctx* ctx) { return ctx ? ctx->eng->row_forwards : -1; }
 int echo_scale_speaker_kv_items(echo_ctx* ctx, const float* scales_host, const int32_t* max_layers_host, int n, void* stream) {
   return ctx ? ctx->eng->scale_speaker_kv_items(scales_host, max_layers_host, n, (hipStream_t)stream) : ECHO_ERR;
 }
@@ -2966,10 +3156,10 @@ int echo_op_pack_rows(const void* src, int sdt, int64_t sld, void* dst, int ddt,
   return op_status(launch_pack_rows(src, sdt, sld, dst, ddt, dld, rows, cols, dst_row0, swiglu_half, (hipStream_t)stream));
 }
 // descriptor -> AttnArgs -> launch, shared by echo_op_attention_bf16 (qlen == nullptr) and echo_op_attention_bf16_len
-static int op_attention_bf16(const echo_attn_desc* d, const int32_t* qlen, void* stream) {
+static int op_attention_bf16(const echo_attn_desc* d, const int32_t* qlen, void* stream, const int32_t* row_item = nullptr) {
   AttnArgs a;
   memset(&a, 0, sizeof(a));
-  a.qlen = qlen;
+  a.qlen = qlen; a.row_item = row_item;
   a.Q = (const bf16_t*)d->Q; a.q_ld = d->q_ld; a.q_row_stride = d->q_row_stride;
   a.O = (bf16_t*)d->O; a.o_ld = d->o_ld; a.o_row_stride = d->o_row_stride;
   a.G = (const bf16_t*)d->G; a.g_ld = d->g_ld; a.g_row_stride = d->g_row_stride;
@@ -2999,6 +3189,15 @@ int echo_op_attention_bf16(const echo_attn_desc* d, void* stream) { return op_at
 int echo_op_attention_bf16_len(const echo_attn_desc* d, const int32_t* qlen_dev, void* stream) {
   if (!d || !qlen_dev) { g_create_error = "echo_op_attention_bf16_len: null descriptor or length table"; return ECHO_ERR; }
   return op_attention_bf16(d, qlen_dev, stream);
+}
+// The same launch under a row map: row r reads the shared KV of item row_item_dev[r].
+int echo_op_attention_bf16_rows(const echo_attn_desc* d, const int32_t* row_item_dev, const int32_t* qlen_dev, void* stream) {
+  if (!d || !row_item_dev) { g_create_error = "echo_op_attention_bf16_rows: null descriptor or row map"; return ECHO_ERR; }
+  if (d->causal || d->O8 || d->prof) {
+    g_create_error = "echo_op_attention_bf16_rows: the row map exists for the joint attention only (no causal mask, no e4m3 output O8, no prof)";
+    return ECHO_ERR;
+  }
+  return op_attention_bf16(d, qlen_dev, stream, row_item_dev);
 }
 int echo_op_norm(int dtype, int mode, const void* x, int64_t ldx, void* y, int64_t ldy, int rows, int D, float eps, const void* w0,
                  const void* w1, void* stream) {

@@ -430,19 +430,25 @@ _NO_VOICE = "\0no-voice"      # cache key of the one-masked-key voice jobs witho
 
 @torch.inference_mode()
 def synthesize_many(job_inputs: List[Dict], model, fish_ae, pca_state, voices=None, max_batch: int = 24, mix_lengths: bool = False,
-                    mix_steps: bool = False) -> List[Dict]:
+                    mix_steps: bool = False, compact_rows: bool = False) -> List[Dict]:
     """Several jobs at once: the text chunks of ALL jobs share sampler calls of up to `max_batch` rows, each row with its own
     request parameters, seed and cached voice (`inference.sample_euler_items`, `EchoDiT.bind_voices`).  Only `num_steps` and
     `sequence_length` cannot be mixed inside a call; jobs are grouped by them (`plan_mixed_batches`).  `mix_lengths=True`: only
     `num_steps` groups; a call runs at its longest row's sequence_length and every shorter row brings its own length
     (`echo_sample_euler_items_len`; a row's noise and result are those of its own length).  `mix_steps=True` (with `mix_lengths=True`):
-    nothing groups; every row also brings its own `num_steps` (`echo_sample_euler_items_steps`).
+    nothing groups; every row also brings its own `num_steps` (`echo_sample_euler_items_steps`).  `compact_rows=True`
+    (default off): every call runs only the rows somebody reads - a `cfg_off` job, or one outside its CFG window, one row
+    instead of three (`sample_euler_items(compact_rows=True)`); EchoHipError on an fp8 model before anything is queued.
 
     `voices`: a `VoiceCache`, or a dict `speaker_voice` name -> (speaker_latent, speaker_mask) or 44.1 kHz audio (1, n); a job
     names its voice with `speaker_voice`, a job without one gets the one-masked-key voice of `sample_pipeline`.  Returns one dict
     per job, in job order: what `synthesize` returns for it, or its own error dict - a bad job does not disturb the others.
     Single-rank: the chunks never enter the data-parallel path of `_run_job`."""
     from .inference import ae_decode, find_flattening_points, get_speaker_latent_and_mask, get_text_input_ids_and_mask, sample_euler_items
+    if compact_rows and getattr(model, "fp8", False):
+        from ._lib import EchoHipError
+        raise EchoHipError("compact_rows: not supported by the fp8 engine (dit_fp8): its e4m3 attention output has no row-map form; "
+                           "use the bf16 engine")
     jobs, calls = plan_mixed_batches(job_inputs, max_batch, mix_lengths=mix_lengths, mix_steps=mix_steps)
     device, dtype, lz = model.device, model.dtype, model.config.latent_size
     cache = voices if isinstance(voices, VoiceCache) else VoiceCache()
@@ -483,10 +489,11 @@ def synthesize_many(job_inputs: List[Dict], model, fish_ae, pca_state, voices=No
                 if steps is not None and len(set(steps)) == 1:
                     steps = None
                 lat = [x.unsqueeze(0) for x in sample_euler_items(model, None, None, ids, tmask, items, sequence_length=lengths, speaker_kv=handles,
-                                                                  num_steps=steps)]
+                                                                  num_steps=steps, compact_rows=compact_rows)]
                 cut = [int(find_flattening_points(x)[0]) for x in lat]
             else:
-                lat = sample_euler_items(model, None, None, ids, tmask, items, sequence_length=call["sequence_length"], speaker_kv=handles)
+                lat = sample_euler_items(model, None, None, ids, tmask, items, sequence_length=call["sequence_length"], speaker_kv=handles,
+                                         compact_rows=compact_rows)
                 cut = find_flattening_points(lat)
             for i, r in enumerate(rows):
                 audio = ae_decode(fish_ae, pca_state, lat[i] if "lengths" in call else lat[i:i + 1])

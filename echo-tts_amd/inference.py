@@ -379,16 +379,43 @@ def step_groups_temb(model: EchoDiT, item_steps: Sequence[int], num_steps: int) 
     return torch.stack(cols, 1).reshape(int(num_steps) * len(cols), -1)
 
 
+def row_forwards(has_cfg_per_item_step, item_steps=None, compact: bool = False) -> int:
+    """Row-forwards (one row through one iteration) of one mixed sampler call; pure host arithmetic.
+    `has_cfg_per_item_step[b][i]`: whether item b has CFG at its own step i (at least item_steps[b] entries).  `item_steps`: None - every
+    item runs all the steps it lists; else one count per item, and the call runs max(item_steps) iterations.
+    Rectangular (`compact=False`): an iteration costs 3 B rows when ANY active item has CFG at it and B rows otherwise, finished items
+    included.  Compacted: an active item costs 3 rows inside its CFG window and 1 outside it, a finished item nothing.
+    `echo_debug_last_row_forwards` reports the same figure for the call that ran."""
+    cfg = [[bool(v) for v in row] for row in has_cfg_per_item_step]
+    B = len(cfg)
+    counts = [len(row) for row in cfg] if item_steps is None else [int(n) for n in item_steps]
+    if len(counts) != B or any(n < 1 or n > len(row) for n, row in zip(counts, cfg)):
+        raise ValueError("row_forwards: one step count per item, 1 <= count <= the item's listed steps")
+    total = 0
+    for i in range(max(counts) if counts else 0):
+        active = [b for b in range(B) if i < counts[b]]
+        if compact:
+            total += sum(3 if cfg[b][i] else 1 for b in active)
+        else:
+            total += 3 * B if any(cfg[b][i] for b in active) else B
+    return total
+
+
 def run_euler_items(model: EchoDiT, x_init: torch.Tensor, item_structs, num_steps: int, temb: Optional[torch.Tensor], start_pos=0,
-                    use_latent: bool = False, lengths=None, item_steps=None) -> torch.Tensor:
+                    use_latent: bool = False, lengths=None, item_steps=None, compact_rows: bool = False) -> torch.Tensor:
     """One echo_sample_euler_items call: `item_structs` is a ctypes array of B EchoSamplerItem.  `start_pos`: one int, or a sequence /
     tensor of B ints - every utterance samples its block at its own position (echo_sample_euler_items_pos).  `lengths`: a sequence / tensor
     of B ints, 1 <= n <= S - item b samples lengths[b] latents; `x_init` beyond them is never read and the result is exactly 0 there
     (echo_sample_euler_items_len).  `item_steps`: a sequence / tensor of B ints, 1 <= n <= num_steps - item b runs item_steps[b] steps of
     its own step table and is left alone afterwards (echo_sample_euler_items_steps); `num_steps` is then the call's maximum and `temb` the
     [N][G] table of `step_groups_temb` (None: built here, one schedule per distinct count).  Items are taken in the order given: put equal
-    step counts next to each other (`sample_euler_items` sorts).  ValueError for what the engine refuses."""
+    step counts next to each other (`sample_euler_items` sorts).  ValueError for what the engine refuses.
+    `compact_rows`: every iteration runs only the rows somebody reads (echo_sample_euler_items_compact); an item's result
+    is then inside the engine's tolerance of, not bit-equal to, the rectangular call's.  EchoHipError on an fp8 model, before anything is queued."""
     B, S, _ = x_init.shape
+    if compact_rows and model.fp8:
+        raise L.EchoHipError("compact_rows: not supported by the fp8 engine (dit_fp8): its e4m3 attention output has no row-map form; "
+                             "use the bf16 engine")
     item_pos = item_start_positions(start_pos, B)
     item_len = item_lengths(lengths, B, S, item_pos if item_pos is not None else start_pos, model.MAX_POS)
     counts = item_step_counts(item_steps, B, int(num_steps))
@@ -404,6 +431,13 @@ def run_euler_items(model: EchoDiT, x_init: torch.Tensor, item_structs, num_step
     p.temb = temb_dev.data_ptr()
     x0 = x_init.to(model.device, torch.float32).contiguous()
     out = torch.empty_like(x0)
+    if compact_rows:
+        pos = (C.c_int32 * B)(*item_pos) if item_pos is not None else None
+        ln = (C.c_int32 * B)(*item_len) if item_len is not None else None
+        cn = (C.c_int32 * B)(*counts) if counts is not None else None
+        L.check(model._lib.echo_sample_euler_items_compact(model._ctx, C.byref(p), item_structs, cn, pos, ln, x0.data_ptr(), out.data_ptr(),
+                                                           model._stream()), model._ctx)
+        return out
     if counts is not None:
         pos = (C.c_int32 * B)(*item_pos) if item_pos is not None else None
         ln = (C.c_int32 * B)(*item_len) if item_len is not None else None
@@ -457,7 +491,7 @@ def _multiply_kv_cache_items(cache: KVHandle, scales, max_layers) -> None:
 
 @torch.inference_mode()
 def sample_euler_items(model: EchoDiT, speaker_latent, speaker_mask, text_input_ids: torch.Tensor, text_mask: torch.Tensor, items, *,
-                       sequence_length=None, x_init: torch.Tensor | None = None, speaker_kv=None, num_steps=None):
+                       sequence_length=None, x_init: torch.Tensor | None = None, speaker_kv=None, num_steps=None, compact_rows: bool = False):
     """reference inference.py:427-517 for B utterances that each bring their OWN request parameters: `items` is a list of B dicts
     with exactly the reference's per-request keys (ITEM_KEYS); row b of the result is what `sample_euler_cfg_independent_guidances`
     computes for row b with items[b].  Per call, not per item: `num_steps` (all items must agree: ValueError).  `sequence_length`: an int
@@ -473,7 +507,14 @@ def sample_euler_items(model: EchoDiT, speaker_latent, speaker_mask, text_input_
     counts are adjacent, and the results come back in the caller's order.  A list of equal values gives the bits of the int form.  A speaker
     cache of batch n with 1 < n < B (rows sharing voice slots) is refused on this path: the sort would move rows to other slots.  Also
     refused (ValueError): rows that share ONE voice (speaker batch 1), use `speaker_kv_scale` and differ in their step counts - each would
-    undo the scale at another iteration, and the shared K / V exist once; give such rows a voice of their own (`speaker_kv=[...]`)."""
+    undo the scale at another iteration, and the shared K / V exist once; give such rows a voice of their own (`speaker_kv=[...]`).
+
+    `compact_rows` (default off): the call runs only the rows somebody reads - an item outside its CFG window one row
+    instead of three, a finished item none (`run_euler_items(compact_rows=True)`).  Results stay inside the engine's tolerance of the
+    rectangular call's; they are not its bits.  EchoHipError on an fp8 model before anything is queued."""
+    if compact_rows and model.fp8:
+        raise L.EchoHipError("compact_rows: not supported by the fp8 engine (dit_fp8): its e4m3 attention output has no row-map form; "
+                             "use the bf16 engine")
     if sequence_length is None:
         sequence_length = 640
     items = [dict(it) for it in items]
@@ -540,9 +581,9 @@ def sample_euler_items(model: EchoDiT, speaker_latent, speaker_mask, text_input_
         x_init = torch.cat([torch.randn((1, sequence_length, lz), device=device, dtype=torch.float32,
                                         generator=torch.Generator(device=device).manual_seed(int(it["rng_seed"]))) for it in items], 0)
     if counts is None:
-        out, rows = run_euler_items(model, x_init, arr, int(items[0]["num_steps"]), temb, lengths=lengths), list(range(B))
+        out, rows = run_euler_items(model, x_init, arr, int(items[0]["num_steps"]), temb, lengths=lengths, compact_rows=compact_rows), list(range(B))
     else:
-        out = run_euler_items(model, x_init, arr, max(counts), None, lengths=lengths, item_steps=counts)
+        out = run_euler_items(model, x_init, arr, max(counts), None, lengths=lengths, item_steps=counts, compact_rows=compact_rows)
         rows = [order.index(b) for b in range(B)]                   # call row of the caller's row b
     if lengths is not None:
         return [out[r, :lengths[r]] for r in rows]

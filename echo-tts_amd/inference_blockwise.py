@@ -133,13 +133,15 @@ def sample_blockwise(model, speaker_latent, speaker_mask, text_input_ids, text_m
 
 
 def stream_audio_many(model: EchoDiT, fish_ae, pca_state, requests, voices=None, max_batch: int = 24, mix_block_sizes: bool = False,
-                      max_pad_fraction=None, mix_steps: bool = False, max_idle_fraction=None) -> Iterator[Tuple[int, torch.Tensor]]:
+                      max_pad_fraction=None, mix_steps: bool = False, max_idle_fraction=None, compact_rows: bool = False) -> Iterator[Tuple[int, torch.Tensor]]:
     """Streaming synthesis of SEVERAL utterances that share sampler calls (`stream_batch.StreamBatcher`): `requests` is a list of dicts
     with the keyword arguments of `StreamBatcher.open` (text_input_ids, text_mask, item_params, block_sizes, rng_seed, speaker_voice,
     continuation_latent, x_inits).  Opens them all and yields `(request index, waveform chunk)` until every stream is done; the chunks of
     one request, concatenated, equal `ae_decode` of its blockwise latent.  `mix_block_sizes=True`: streams whose next blocks differ in size
     share a call too, within `max_pad_fraction` padded tokens per call (`StreamBatcher`).  `mix_steps=True` (with `mix_block_sizes=True`):
-    streams of different `num_steps` share a call as well, within `max_idle_fraction` idle steps per call."""
+    streams of different `num_steps` share a call as well, within `max_idle_fraction` idle steps per call.  `compact_rows=True` (default
+    off): the calls run only the rows somebody reads."""
     from .stream_batch import stream_audio_many as _many
     yield from _many(model, fish_ae, pca_state, requests, voices=voices, max_batch=max_batch, mix_block_sizes=mix_block_sizes,
-                     max_pad_fraction=max_pad_fraction, mix_steps=mix_steps, max_idle_fraction=max_idle_fraction)
+                     max_pad_fraction=max_pad_fraction, mix_steps=mix_steps, max_idle_fraction=max_idle_fraction,
+                     compact_rows=compact_rows)

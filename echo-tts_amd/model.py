@@ -290,6 +290,10 @@ class EchoDiT:
     def eval(self) -> "EchoDiT":
         return self
 
+    def last_row_forwards(self) -> int:
+        """Sum of `rows` over the forwards of the last sampler call on this model (echo_debug_last_row_forwards; `inference.row_forwards`)."""
+        return int(self._lib.echo_debug_last_row_forwards(self._ctx))
+
     def _stream(self) -> int:
         return torch.cuda.current_stream(self._device).cuda_stream
 
@@ -437,14 +441,21 @@ class EchoDiT:
     # ------------------------------------------------------------------ forward (model.py:563-604)
     def forward(self, x: torch.Tensor, t: torch.Tensor, text_mask: torch.Tensor, speaker_mask: torch.Tensor,
                 kv_cache_text: KVHandle, kv_cache_speaker: KVHandle, start_pos=None,
-                kv_cache_latent: Optional[KVHandle] = None, lengths=None) -> torch.Tensor:
+                kv_cache_latent: Optional[KVHandle] = None, lengths=None, row_item=None) -> torch.Tensor:
         """`start_pos`: None / an int as in the reference, or (extension) a sequence or tensor of B ints, one per KV batch item: row r is
         then evaluated at start_pos[r % B] (streams of one batch that stand at different blocks, `echo_dit_forward_pos`).
         `lengths` (extension): a sequence or tensor of B ints, 1 <= n <= S: item b owns the first lengths[b] tokens of its rows, the rest is
-        padding that is never read and comes back as zeros (`echo_dit_forward_len`).  Not with `fp8=True` (EchoHipError)."""
+        padding that is never read and comes back as zeros (`echo_dit_forward_len`).  Not with `fp8=True` (EchoHipError).
+        `row_item` (extension): a sequence of `rows` ints in [0, B) - row r uses the position, length, text and speaker KV of
+        item row_item[r] instead of r % B; `rows` is then any value in 1..96 (`echo_dit_forward_rows`).  A row's masks are checked against
+        its item's cached masks.  Not with `fp8=True` (EchoHipError)."""
         rows, S, Lz = x.shape
         B = self._kvB
-        if rows % B:
+        if row_item is not None:
+            row_item = [int(v) for v in (row_item.tolist() if isinstance(row_item, torch.Tensor) else row_item)]
+            if len(row_item) != rows:
+                raise ValueError(f"row_item must have one entry per row ({rows}), got {len(row_item)}")
+        elif rows % B:
             raise ValueError("batch rows must be a multiple of the KV batch")
         item_pos = item_start_positions(start_pos, B)
         item_len = item_lengths(lengths, B, S, item_pos if item_pos is not None else start_pos, self.MAX_POS)
@@ -463,10 +474,17 @@ class EchoDiT:
             row_t.append(uniq.index(v))
         temb = timestep_embedding(torch.tensor(uniq, dtype=torch.float32).to(self._dtype), self.config.timestep_embed_size)
         temb = temb.to(self._device).contiguous()
-        ton = self._row_switch(text_mask, kv_cache_text.mask, rows, B, 1)
-        son = self._row_switch(speaker_mask, kv_cache_speaker.mask, rows, kv_cache_speaker.batch, self.config.speaker_patch_size)
+        ton = self._row_switch(text_mask, kv_cache_text.mask, rows, B, 1, row_item)
+        son = self._row_switch(speaker_mask, kv_cache_speaker.mask, rows, kv_cache_speaker.batch, self.config.speaker_patch_size, row_item)
         xin = x.to(self._device, self._dtype).contiguous()
         out = torch.empty((rows, S, Lz), dtype=torch.float32, device=self._device)
+        if row_item is not None:
+            i32 = C.c_int32
+            L.check(self._lib.echo_dit_forward_rows(self._ctx, xin.data_ptr(), temb.data_ptr(), len(uniq), (i32 * rows)(*row_t), rows, B, S,
+                                                    (i32 * rows)(*row_item), (i32 * B)(*item_pos) if item_pos is not None else None,
+                                                    (i32 * B)(*item_len) if item_len is not None else None, int(kv_cache_latent is not None),
+                                                    (i32 * rows)(*ton), (i32 * rows)(*son), out.data_ptr(), self._stream()), self._ctx)
+            return out
         if item_len is not None:
             pos = item_pos if item_pos is not None else [int(start_pos or 0)] * B
             L.check(self._lib.echo_dit_forward_len(self._ctx, xin.data_ptr(), temb.data_ptr(), len(uniq), (C.c_int32 * rows)(*row_t), rows, B, S,
@@ -486,14 +504,15 @@ class EchoDiT:
     __call__ = forward
 
     @staticmethod
-    def _row_switch(mask: torch.Tensor, cached: Optional[torch.Tensor], rows: int, B: int, stride: int) -> List[int]:
-        """Each row's mask must equal the mask the cache was built with (segment on) or be all False (segment off)."""
+    def _row_switch(mask: torch.Tensor, cached: Optional[torch.Tensor], rows: int, B: int, stride: int, row_item=None) -> List[int]:
+        """Each row's mask must equal the mask the cache was built with (segment on) or be all False (segment off).  `row_item`: the
+        rows' items under a row map (None: row r belongs to item r % B)."""
         m = mask.detach().to("cpu", torch.bool)[..., ::stride]
         on = []
         for r in range(rows):
             if not bool(m[r].any()):
                 on.append(0)
-            elif cached is None or torch.equal(m[r], cached[r % B]):
+            elif cached is None or torch.equal(m[r], cached[(r if row_item is None else row_item[r]) % B]):
                 on.append(1)
             else:
                 raise NotImplementedError("per-row key masks other than the cached mask or all-False are not supported")

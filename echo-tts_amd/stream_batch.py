@@ -90,15 +90,18 @@ def padded_share(block_sizes: Sequence[int]) -> float:
     return sum(s_call - int(b) for b in block_sizes) / float(n * s_call)
 
 
-def idle_share(step_counts: Sequence[int]) -> float:
+def idle_share(step_counts: Sequence[int], compact: bool = False) -> float:
     """sum(N - n_i) / (n * N) of one call, N = the largest step count in it: the share of its (stream, iteration) pairs in which a stream
-    has already finished and only rides along."""
+    has already finished and only rides along.  `compact=True` (a call with compacted row sets): a finished stream has no
+    rows, nothing rides along: 0."""
+    if compact:
+        return 0.0
     n, top = len(step_counts), max(int(v) for v in step_counts)
     return sum(top - int(v) for v in step_counts) / float(n * top)
 
 
 def plan_stream_step_mixed(states: Sequence[StreamState], max_batch: int, max_pad_fraction: Optional[float] = None, mix_steps: bool = False,
-                           max_idle_fraction: Optional[float] = None) -> List[int]:
+                           max_idle_fraction: Optional[float] = None, compact: bool = False) -> List[int]:
     """`plan_stream_step` for calls that mix block sizes: the key of a call is `num_steps` alone.  Pure function of the states.
 
     The leader is chosen as there (longest wait, ties by arrival).  The call is filled in arrival order with open streams of the leader's
@@ -107,7 +110,8 @@ def plan_stream_step_mixed(states: Sequence[StreamState], max_batch: int, max_pa
 
     `mix_steps=True`: the key of a call is empty - every open stream is a candidate whatever its `num_steps`.  Leader rule and arrival order
     are unchanged; a candidate is also skipped when taking it would raise the call's idle share (`idle_share` of the step counts taken so far
-    plus its own) above `max_idle_fraction` (None: no limit)."""
+    plus its own) above `max_idle_fraction` (None: no limit).  `compact=True`: the calls compact their row sets (`idle_share(compact=True)`
+    is 0), so the idle limit skips nobody."""
     cap = max(1, min(int(max_batch), MAX_ITEMS))
     open_ = [s for s in states if not s.finished]
     if not open_:
@@ -119,7 +123,7 @@ def plan_stream_step_mixed(states: Sequence[StreamState], max_batch: int, max_pa
             break
         if max_pad_fraction is not None and padded_share(sizes + [s.key[0]]) > float(max_pad_fraction):
             continue
-        if mix_steps and max_idle_fraction is not None and idle_share(counts + [int(s.num_steps)]) > float(max_idle_fraction):
+        if mix_steps and max_idle_fraction is not None and idle_share(counts + [int(s.num_steps)], compact) > float(max_idle_fraction):
             continue
         picked.append(s.id)
         sizes.append(s.key[0])
@@ -167,12 +171,21 @@ class StreamBatcher:
     `batch_decode=True`: `step_audio()` decodes the step's blocks in one `DACStream.push_many` call instead of one `push` per stream.
 
     `mix_steps=True` (needs `mix_block_sizes=True`: ValueError otherwise): streams with different `num_steps` share a call too, bounded by
-    `max_idle_fraction`; the call's rows are ordered by step count, longest first, and `stats["idle_steps"]` counts the ride-along steps."""
+    `max_idle_fraction`; the call's rows are ordered by step count, longest first, and `stats["idle_steps"]` counts the ride-along steps.
+
+    `compact_rows=True` (default off): every sampler call runs only the rows somebody reads (`run_euler_items(compact_rows=True)`):
+    a finished stream has none, `max_idle_fraction` then limits nothing and `stats["idle_steps"]` stays 0.  `stats["row_forwards"]` counts the
+    rows the calls' forwards ran, with or without it.  EchoHipError on an fp8 model, at construction."""
 
     def __init__(self, model, fish_ae, pca_state, voices=None, max_batch: int = 24, mix_block_sizes: bool = False,
                  max_pad_fraction: Optional[float] = None, batch_decode: bool = False, mix_steps: bool = False,
-                 max_idle_fraction: Optional[float] = None):
+                 max_idle_fraction: Optional[float] = None, compact_rows: bool = False):
         from .handler import VoiceCache
+        from ._lib import EchoHipError
+        if compact_rows and getattr(model, "fp8", False):
+            raise EchoHipError("compact_rows: not supported by the fp8 engine (dit_fp8): its e4m3 attention output has no row-map form; "
+                               "use the bf16 engine")
+        self.compact_rows = bool(compact_rows)
         if mix_steps and not mix_block_sizes:
             raise ValueError("mix_steps=True requires mix_block_sizes=True: a call that mixes step counts is planned by plan_stream_step_mixed")
         self.mix_steps, self.max_idle_fraction = bool(mix_steps), max_idle_fraction
@@ -187,7 +200,8 @@ class StreamBatcher:
         self._tick = 0
         # ms_*: filled when `timing` is set (adds synchronisation); tokens / pad_tokens: token rows the calls carried / of them padding
         # steps / idle_steps: (stream, iteration) pairs the calls ran / of them past the stream's own last step
-        self.stats = {"calls": 0, "rows": 0, "ms_encode": 0.0, "ms_sample": 0.0, "tokens": 0, "pad_tokens": 0, "steps": 0, "idle_steps": 0}
+        self.stats = {"calls": 0, "rows": 0, "ms_encode": 0.0, "ms_sample": 0.0, "tokens": 0, "pad_tokens": 0, "steps": 0, "idle_steps": 0,
+                      "row_forwards": 0}
         self.timing = False
 
     # ------------------------------------------------------------------ voices
@@ -270,7 +284,7 @@ class StreamBatcher:
     def _step(self) -> List[Tuple[int, int, torch.Tensor]]:
         from .inference import _multiply_kv_cache_items, build_sampler_items, check_sampler_items, check_sampler_items_steps, run_euler_items
         if self.mix_block_sizes:
-            picked = plan_stream_step_mixed(list(self._streams.values()), self.max_batch, self.max_pad_fraction, mix_steps=self.mix_steps,
+            picked = plan_stream_step_mixed(list(self._streams.values()), self.max_batch, self.max_pad_fraction, mix_steps=self.mix_steps, compact=self.compact_rows,
                                             max_idle_fraction=self.max_idle_fraction)
         else:
             picked = plan_stream_step(list(self._streams.values()), self.max_batch)
@@ -325,11 +339,12 @@ class StreamBatcher:
             ev[1].record()
         if mixed_steps:
             x = run_euler_items(m, x0, arr, max(counts), None, start_pos=starts, use_latent=True, lengths=sizes if mixed else None,
-                                item_steps=counts)
+                                item_steps=counts, compact_rows=self.compact_rows)
         elif mixed:
-            x = run_euler_items(m, x0, arr, rows[0].num_steps, temb, start_pos=starts, use_latent=True, lengths=sizes)
+            x = run_euler_items(m, x0, arr, rows[0].num_steps, temb, start_pos=starts, use_latent=True, lengths=sizes, compact_rows=self.compact_rows)
         else:
-            x = run_euler_items(m, x0, arr, rows[0].num_steps, temb, start_pos=starts, use_latent=True)
+            x = run_euler_items(m, x0, arr, rows[0].num_steps, temb, start_pos=starts, use_latent=True, compact_rows=self.compact_rows)
+        self.stats["row_forwards"] += m.last_row_forwards()
         if self.timing:
             ev[2].record()
             torch.cuda.synchronize(m.device)
@@ -340,7 +355,7 @@ class StreamBatcher:
         self.stats["tokens"] += B * max(sizes)
         self.stats["pad_tokens"] += B * max(sizes) - sum(sizes)
         self.stats["steps"] += B * max(counts)
-        self.stats["idle_steps"] += B * max(counts) - sum(counts)
+        self.stats["idle_steps"] += 0 if self.compact_rows else B * max(counts) - sum(counts)
         self._tick += 1
         out = []
         for b, s in enumerate(rows):
@@ -399,12 +414,13 @@ class StreamBatcher:
 
 def stream_audio_many(model, fish_ae, pca_state, requests: Sequence[dict], voices=None, max_batch: int = 24, mix_block_sizes: bool = False,
                       max_pad_fraction: Optional[float] = None, batch_decode: bool = False, mix_steps: bool = False,
-                      max_idle_fraction: Optional[float] = None) -> Iterator[Tuple[int, torch.Tensor]]:
+                      max_idle_fraction: Optional[float] = None, compact_rows: bool = False) -> Iterator[Tuple[int, torch.Tensor]]:
     """Generator over a list of requests (dicts with the keyword arguments of `StreamBatcher.open`): opens them all and yields
     `(request index, waveform chunk)` block by block until every stream is done.  `mix_block_sizes` / `max_pad_fraction` / `batch_decode` /
-    `mix_steps` / `max_idle_fraction`: `StreamBatcher`."""
+    `mix_steps` / `max_idle_fraction` / `compact_rows`: `StreamBatcher`."""
     sb = StreamBatcher(model, fish_ae, pca_state, voices=voices, max_batch=max_batch, mix_block_sizes=mix_block_sizes,
-                       max_pad_fraction=max_pad_fraction, batch_decode=batch_decode, mix_steps=mix_steps, max_idle_fraction=max_idle_fraction)
+                       max_pad_fraction=max_pad_fraction, batch_decode=batch_decode, mix_steps=mix_steps, max_idle_fraction=max_idle_fraction,
+                       compact_rows=compact_rows)
     index = {sb.open(**dict(r)): i for i, r in enumerate(requests)}
     while sb.open_ids:
         for sid, chunk in sb.step_audio():

@@ -268,6 +268,37 @@ int echo_sample_euler_items_steps(echo_ctx* ctx, const echo_sampler_params* p, c
                                   const int32_t* item_steps /* host, p->B */, const int32_t* item_start_pos /* host, p->B, may be NULL */,
                                   const int32_t* item_len /* host, p->B, may be NULL */, const float* x_init, float* latent_out, void* stream);
 
+/* ---- compacted row sets: a row-to-item map through the forward (additive: every declaration above keeps its layout, its bits and its refusals;
+ * ECHO_ABI_VERSION stays 8) ----
+ * The calls above address the text, speaker and latent caches, the positions and the lengths by `row % B`, which forces the rectangular B / 3 B
+ * row set on every forward.  These take the rows as a MAP: row r belongs to item row_item[r].
+ *   - echo_dit_forward_rows: `rows` is any value in 1..96 and need not be a multiple of B; an item may own zero, one or several rows.  Row r takes the
+ *     start position, the length, the latent-prefix count, the text keys and the speaker slot of item row_item[r]; x, row_t, row_text_on,
+ *     row_spk_on and v_out stay indexed by the row.  item_start_pos / item_len (B entries, per ITEM) may each be NULL: position 0 / all S tokens.
+ *     With the rectangular map (row_item[r] = r % B) the bits of echo_dit_forward_t / _pos / _len.  Two forwards with the same `rows` and the same
+ *     runs of row_t agree on any row that has the same item, flags, timestep and x, wherever it stands.
+ *   - echo_sample_euler_items_compact: echo_sample_euler_items_steps (same tables, same groups, same temb [N][G], same refusals; item_steps may be
+ *     NULL: every item runs p->num_steps) whose iteration i runs ONLY the rows somebody reads: the conditional row of every ACTIVE item, and its
+ *     text-uncond and speaker-uncond rows if and only if it has CFG at its own step i.  A finished item contributes nothing.  Row order:
+ *     group-major (step-count groups in order of first appearance), inside a group conditional, then text-uncond, then speaker-uncond rows, items
+ *     in call order: one launch of the modulation-reading kernels per ACTIVE group.  All distinct row sets of the call are planned on the host
+ *     and their tables go to the device in the call's one staged copy, in front of the loop.
+ *   - one group and every item in CFG at the same steps: the bits of echo_sample_euler_items_len / _steps.  An item's result does not depend on
+ *     the other items' contents while their row sets stay the same.  NOT claimed: that an item has the bits of the rectangular or of a uniform
+ *     call (other row counts, other M, other GEMM plans).
+ *   - echo_debug_last_row_forwards: the sum of `rows` over the forwards of the last sampler call of ANY sampler entry point (test instrument).
+ * Fail (non-zero, echo_last_error; nothing is queued, the context stays usable) on a NULL row_item, an entry outside [0, B), rows outside 1..96,
+ * a context created with dit_fp8 (the e4m3 attention output has no row-map form), and on everything the calls they extend fail on. */
+int echo_dit_forward_rows(echo_ctx* ctx, const void* x, const void* temb, int n_t, const int32_t* row_t, int rows, int B, int S,
+                          const int32_t* row_item /* host, rows; 0 <= row_item[r] < B */, const int32_t* item_start_pos /* host, B, may be NULL */,
+                          const int32_t* item_len /* host, B, may be NULL */, int use_latent, const int32_t* row_text_on, const int32_t* row_spk_on,
+                          float* v_out, void* stream);
+int echo_sample_euler_items_compact(echo_ctx* ctx, const echo_sampler_params* p, const echo_sampler_item* items /* p->B entries */,
+                                    const int32_t* item_steps /* host, p->B, may be NULL: all p->num_steps */,
+                                    const int32_t* item_start_pos /* host, p->B, may be NULL */, const int32_t* item_len /* host, p->B, may be NULL */,
+                                    const float* x_init, float* latent_out, void* stream);
+int64_t echo_debug_last_row_forwards(echo_ctx* ctx);
+
 /* inference.py:226-229 ae_decode -> autoencoder.py:1128-1132 DAC.decode_zq, one batch item:
  * latent (T, latent_size) fp32 -> wav (T * hop) fp32.
  * ECHO_BF16 context (ABI 8): the PCA inverse is evaluated in fp32 and rounded to bf16 once (inference.py:227-229), the decoder runs in bf16 and the
@@ -393,6 +424,11 @@ int echo_op_attention_bf16(const echo_attn_desc* d, void* stream);
  * The self segment's key counts are the caller's (the engine passes nkeys = qlen); K / Vt at padding positions must be finite.  A NULL
  * table, causal, O8, prof or a per-key bias together with a table fail with a status and a message (echo_last_error(NULL)). */
 int echo_op_attention_bf16_len(const echo_attn_desc* d, const int32_t* qlen_dev, void* stream);
+/* The same launch under a row map (additive under ABI 8): row_item_dev[r] (device, d->rows entries) is the batch item whose shared
+ * KV row r reads: in every segment with kv_mod > 0 the KV row - and the row of the per-key bias - is row_item_dev[r] % kv_mod.  The self segment
+ * (kv_mod 0), nkeys, qlen_dev, Q, O and G stay indexed by r.  Row r has the bits of the launch above run on KV physically gathered for row r.
+ * qlen_dev may be NULL.  A NULL map, causal, O8 or prof fail with a status and a message (echo_last_error(NULL)). */
+int echo_op_attention_bf16_rows(const echo_attn_desc* d, const int32_t* row_item_dev, const int32_t* qlen_dev /* may be NULL */, void* stream);
 
 int echo_op_norm(int dtype, int mode, const void* x, int64_t ldx, void* y, int64_t ldy, int rows, int D, float eps,
                  const void* w0, const void* w1, void* stream);

@@ -94,23 +94,25 @@ def mixed_vs_grouped(model, inf, n_each, N, n_fast, warmup, repeats, g):
     counts = [N] * n_each + [n_fast] * n_each            # longest first: equal counts adjacent
     items = [dict(BASE, num_steps=n, rng_seed=b) for b, n in enumerate(counts)]
 
-    def call(rows, item_steps):
+    def call(rows, item_steps, compact=False):
         model.get_kv_cache_text(ids[rows], tmask[rows])
         model.get_kv_cache_speaker(spk[rows], smask[rows])
         its = [items[b] for b in rows]
         arr, temb, _keep = inf.build_sampler_items(model, its)
         if item_steps:
             return inf.run_euler_items(model, x0[rows], arr, max(counts[b] for b in rows), None, lengths=[S] * len(rows),
-                                       item_steps=[counts[b] for b in rows])
+                                       item_steps=[counts[b] for b in rows], compact_rows=compact)
         return inf.run_euler_items(model, x0[rows], arr, counts[rows[0]], temb, lengths=[S] * len(rows))
 
     slow, fast = list(range(n_each)), list(range(n_each, B))
     cases = {"grouped": lambda: torch.cat([call(slow, False), call(fast, False)], 0),
-             "mixed": lambda: call(slow + fast, True)}
-    times, last = {k: [] for k in cases}, {}
+             "mixed": lambda: call(slow + fast, True),
+             "compact": lambda: call(slow + fast, True, compact=True)}      # the mixed call with compacted row sets
+    times, last, row_forwards = {k: [] for k in cases}, {}, {}
     for r in range(warmup + repeats):
         for name, fn in cases.items():
             ms, last[name] = timed(fn)
+            row_forwards[name] = model.last_row_forwards()       # grouped: of its second call only
             note(f"(b) {name} run {r}: {ms:.1f} ms")
             if r >= warmup:
                 times[name].append(ms)
@@ -128,6 +130,14 @@ def mixed_vs_grouped(model, inf, n_each, N, n_fast, warmup, repeats, g):
     out["mixed_vs_grouped_rms"] = [round(float(d[b].pow(2).mean().sqrt()), 6) for b in range(B)]
     out["latent_rms"] = round(float(last["grouped"].float().pow(2).mean().sqrt()), 4)
     out["finite"] = bool(torch.isfinite(last["mixed"]).all())
+    cm = out["compact"]["median_ms"]
+    out["compact_minus_grouped_ms"] = round(cm - gm, 3)
+    out["compact_minus_grouped_pct"] = round(100 * (cm - gm) / gm, 3)
+    out["compact_minus_mixed_pct"] = round(100 * (cm - mm) / mm, 3)
+    dc = (last["compact"].float() - last["grouped"].float())
+    out["compact_vs_grouped_rms"] = [round(float(dc[b].pow(2).mean().sqrt()), 6) for b in range(B)]
+    out["row_forwards"] = {"mixed": row_forwards["mixed"], "compact": row_forwards["compact"]}
+    out["compact_finite"] = bool(torch.isfinite(last["compact"]).all())
     return out
 
 
@@ -138,6 +148,7 @@ def main() -> None:
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--only-mixed", action="store_true", help="case (b) alone: grouped / mixed / compacted")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("tools/bench_item_steps.py needs an MI355X: the hot path has no CPU fallback")
@@ -151,7 +162,7 @@ def main() -> None:
     torch.cuda.empty_cache()
     note("model ready")
     g = torch.Generator().manual_seed(1234)
-    cost = [steps_form_cost(model, inf, B, args.steps, args.warmup, args.repeats, g) for B in (8, 24)]
+    cost = [] if args.only_mixed else [steps_form_cost(model, inf, B, args.steps, args.warmup, args.repeats, g) for B in (8, 24)]
     mix = mixed_vs_grouped(model, inf, 4, args.steps, args.fast_steps, args.warmup, args.repeats, g)
     rec = {"tool": "tools/bench_item_steps.py", "device": torch.cuda.get_device_name(0),
            "workload": f"full-size EchoDiT, random bf16 weights, S = {S}, {TVALID} of {TT} text tokens, speaker references of {TS} latents; "

@@ -8,6 +8,12 @@ synchronise; the three cases ALTERNATE inside every repeat, so drift of the box 
   distinct  echo_sample_euler_items, 24 different parameter sets inside one CFG window (scales, truncation, rescale)
 Reported: median / min / max per case, the uniform call's run-to-run spread, and the overhead of the two mixed cases over it.
 
+cfg_off among CFG items: half of the items have no CFG window (cfg_min_t above 1), the others BASE's; the rectangular
+echo_sample_euler_items call pays 3 rows for everybody while the window is open, the compacted call (compact_rows=True) 1 row for a cfg_off
+item:
+  cfgoff_rect     echo_sample_euler_items            cfgoff_compact  echo_sample_euler_items_compact
+Reported with the row-forwards of both calls; `--only-cfg-off` runs this section alone.
+
 Voices (24 voices of 1280..2560 speaker latents, captured once):
   bind      EchoDiT.bind_voices: one gather kernel into a batch-24 speaker cache
   encode    get_kv_cache_speaker on the 24 stacked, padded latents with masks (what a server without the per-voice cache runs)
@@ -70,6 +76,7 @@ def main() -> None:
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--only-cfg-off", action="store_true", help="the cfg_off-among-CFG section alone")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("tools/bench_mixed_batch.py needs an MI355X: the hot path has no CPU fallback")
@@ -95,10 +102,39 @@ def main() -> None:
         smask[b, :n] = True
     x0 = torch.randn((B, S, cfg.latent_size), generator=g).to(device)
 
-    # ------------------------------------------------------------------ sampler: uniform call vs mixed call, caches in place
+    # ------------------------------------------------------------------ cfg_off items among CFG items: rectangular vs compacted rows
     kw = dict(BASE, num_steps=N)
     model.get_kv_cache_text(ids, tmask)
     model.get_kv_cache_speaker(spk, smask)
+    off_items = [dict(kw, rng_seed=b, cfg_min_t=1.1 if b % 2 else kw["cfg_min_t"]) for b in range(B)]
+    off, off_temb, keep_off = inf.build_sampler_items(model, off_items)
+    ocases = {"cfgoff_rect": lambda: inf.run_euler_items(model, x0, off, N, off_temb),
+              "cfgoff_compact": lambda: inf.run_euler_items(model, x0, off, N, off_temb, compact_rows=True)}
+    otimes, olast, orows = {k: [] for k in ocases}, {}, {}
+    for r in range(args.warmup + args.repeats):
+        for name, fn in ocases.items():
+            ms, olast[name] = timed(fn)
+            orows[name] = model.last_row_forwards()
+            note(f"{name} run {r}: {ms:.1f} ms")
+            if r >= args.warmup:
+                otimes[name].append(ms)
+    audio_s = B * S * 2048 / 44100.0
+    cfg_off = {k: dict(stats(v), audio_s_per_s=round(audio_s / (statistics.median(v) * 1e-3), 2), row_forwards=orows[k]) for k, v in otimes.items()}
+    cfg_off["items"] = f"{B - B // 2} x CFG window {kw['cfg_min_t']}..{kw['cfg_max_t']} + {B // 2} x cfg_off, {N} steps"
+    cfg_off["compact_minus_rect_pct"] = round(100 * (cfg_off["cfgoff_compact"]["median_ms"] / cfg_off["cfgoff_rect"]["median_ms"] - 1), 3)
+    d_off = olast["cfgoff_compact"].float() - olast["cfgoff_rect"].float()
+    cfg_off["compact_vs_rect_rms_max"] = round(max(float(d_off[b].pow(2).mean().sqrt()) for b in range(B)), 6)
+    cfg_off["finite"] = bool(torch.isfinite(olast["cfgoff_compact"]).all())
+    if args.only_cfg_off:
+        rec = {"tool": "tools/bench_mixed_batch.py", "device": torch.cuda.get_device_name(0), "cfg_off_among_cfg": cfg_off}
+        print(json.dumps(rec))
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w", encoding="utf-8") as f:
+                f.write(json.dumps(rec, indent=1) + "\n")
+        return
+
+    # ------------------------------------------------------------------ sampler: uniform call vs mixed call, caches in place
     steps, temb = inf.build_schedule(model, N, kw["cfg_min_t"], kw["cfg_max_t"], None, None, None, None)
     same, _, keep_same = inf.build_sampler_items(model, [dict(kw, rng_seed=0)] * B)
     dist_items = distinct_items(B, N)
@@ -161,7 +197,7 @@ def main() -> None:
            "workload": f"C2 shapes: full-size EchoDiT, random bf16 weights, B = {B} utterances per sampler call, S = {S}, {N} Euler steps, "
                        f"{TVALID} of {TT} text tokens, speaker references of {min(lens)}..{max(lens)} latents; {args.warmup} warm-up + {args.repeats} "
                        f"timed repeats, cases alternating inside a repeat, host clock around a device synchronise",
-           "sampler": sampler, "voices": voice}
+           "sampler": sampler, "voices": voice, "cfg_off_among_cfg": cfg_off}
     line = json.dumps(rec)
     print(line)
     if args.out:
