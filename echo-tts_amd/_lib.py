@@ -183,6 +183,13 @@ SIGNATURES = {
     "echo_op_trailing_quiet": (C.c_int, [C.POINTER(vp), C.POINTER(c_i64), C.c_int, C.c_int, C.c_float, vp, vp]),
     "echo_op_assemble_chunks": (C.c_int, [C.POINTER(vp), C.POINTER(c_i64), C.POINTER(c_i64), C.POINTER(c_i64), C.POINTER(C.c_int32),
                                           C.c_int, vp, c_i64, vp]),
+    "echo_op_dac_dwconv_ln": (C.c_int, [C.c_int, vp, c_i64, vp, c_i64, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.c_float, vp]),
+    "echo_op_dac_conv_out_tanh": (C.c_int, [C.c_int, vp, c_i64, vp, c_i64, C.c_int, C.c_int, C.c_int, vp, C.c_float, vp]),
+    "echo_op_dac_snake": (C.c_int, [vp, c_i64, vp, c_i64, c_i64, C.c_int, vp, vp]),
+    "echo_op_dac_rope": (C.c_int, [C.c_int, vp, c_i64, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
+    "echo_op_dac_conv_in_snake": (C.c_int, [vp, c_i64, C.c_int, C.c_int, vp, vp, vp, vp, vp, c_i64, vp]),
+    "echo_op_dac_vq_argmax": (C.c_int, [vp, c_i64, C.c_int, vp, vp, C.c_int, vp, vp, c_i64, vp, c_i64, vp]),
+    "echo_op_softmax": (C.c_int, [C.c_int, vp, c_i64, C.c_int, c_i64, C.c_int, C.c_int, vp, c_i64, C.c_int, C.c_int, C.c_int, vp]),
     "echo_set_profiling": (C.c_int, [vp, C.c_int]),
     "echo_get_profile": (C.c_int, [vp, C.POINTER(EchoProfile)]),
 }

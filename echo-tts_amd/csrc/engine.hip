@@ -3223,6 +3223,83 @@ int echo_op_transpose_heads(int dtype, const void* v, int64_t ldv, void* vt, int
                        : launch_transpose_heads<float>((const float*)v, ldv, (float*)vt, vt_ld, vt_b_stride, B, S, H, HD, st));
 }
 
+// ---- the DAC's small kernels and the two softmaxes, one launch each (tests/test_gpu_dac_kernels.py).  The wrappers refuse what the launchers
+// leave to the engine's own shapes; the engine path calls the launchers directly and stays as it is.
+static int op_refuse(const char* what) {
+  g_create_error = what;
+  return ECHO_ERR;
+}
+static bool op_dtype_ok(int dtype) { return dtype == ECHO_F32 || dtype == ECHO_BF16; }
+
+int echo_op_dac_dwconv_ln(int dtype, const void* x, int64_t ldx, void* y, int64_t ldy, int T, int S, int C, const void* w, const void* b,
+                          const void* lnw, const void* lnb, float eps, void* stream) {
+  if (!x || !y || !w || !b || !lnw || !lnb) return op_refuse("echo_op_dac_dwconv_ln: null operand");
+  if (!op_dtype_ok(dtype)) return op_refuse("echo_op_dac_dwconv_ln: dtype must be ECHO_F32 or ECHO_BF16");
+  if (T < 1 || S < 1 || C < 4 || (C & 3) || C > 1024 || ldx < C || ldy < C || (ldx & 3) || (ldy & 3))
+    return op_refuse("echo_op_dac_dwconv_ln: needs T, S >= 1, C % 4 == 0, 4 <= C <= 1024, ldx, ldy >= C and % 4 == 0");
+  hipStream_t st = (hipStream_t)stream;
+  return op_status(dtype == ECHO_BF16
+                       ? launch_dwconv_ln<bf16_t>((const bf16_t*)x, ldx, (bf16_t*)y, ldy, T, S, C, (const bf16_t*)w, (const bf16_t*)b,
+                                                  (const bf16_t*)lnw, (const bf16_t*)lnb, eps, st)
+                       : launch_dwconv_ln<float>((const float*)x, ldx, (float*)y, ldy, T, S, C, (const float*)w, (const float*)b,
+                                                 (const float*)lnw, (const float*)lnb, eps, st));
+}
+int echo_op_dac_conv_out_tanh(int dtype, const void* x, int64_t ldx, float* y_f32, int64_t T, int S, int C, int k, const void* w, float bias,
+                              void* stream) {
+  if (!x || !y_f32 || !w) return op_refuse("echo_op_dac_conv_out_tanh: null operand");
+  if (!op_dtype_ok(dtype)) return op_refuse("echo_op_dac_conv_out_tanh: dtype must be ECHO_F32 or ECHO_BF16");
+  if (T < 1 || S < 1 || C < 4 || (C & 3) || C > 128 || k < 1 || k > 8 || ldx < C || (ldx & 3))
+    return op_refuse("echo_op_dac_conv_out_tanh: needs T, S >= 1, C % 4 == 0, 4 <= C <= 128, 1 <= k <= 8, ldx >= C and % 4 == 0");
+  hipStream_t st = (hipStream_t)stream;
+  return op_status(dtype == ECHO_BF16 ? launch_conv_out_tanh<bf16_t>((const bf16_t*)x, ldx, y_f32, (long)T, S, C, k, (const bf16_t*)w, bias, st)
+                                      : launch_conv_out_tanh<float>((const float*)x, ldx, y_f32, (long)T, S, C, k, (const float*)w, bias, st));
+}
+int echo_op_dac_snake(const float* x, int64_t ldx, float* y, int64_t ldy, int64_t rows, int C, const float* alpha, void* stream) {
+  if (!x || !y || !alpha) return op_refuse("echo_op_dac_snake: null operand");
+  if (rows < 1 || C < 1 || ldx < C || ldy < C) return op_refuse("echo_op_dac_snake: needs rows, C >= 1, ldx, ldy >= C");
+  return op_status(launch_snake_f32(x, ldx, y, ldy, (long)rows, C, alpha, (hipStream_t)stream));
+}
+int echo_op_dac_rope(int dtype, void* x, int64_t ldx, int rows, int S, int H, int HD, const float* cache, void* stream) {
+  if (!x || !cache) return op_refuse("echo_op_dac_rope: null operand");
+  if (!op_dtype_ok(dtype)) return op_refuse("echo_op_dac_rope: dtype must be ECHO_F32 or ECHO_BF16");
+  if (rows < 1 || S < 1 || H < 1 || HD < 2 || (HD & 1) || ldx < (int64_t)H * HD)
+    return op_refuse("echo_op_dac_rope: needs rows, S, H >= 1, HD >= 2 and even, ldx >= H * HD");
+  hipStream_t st = (hipStream_t)stream;
+  return op_status(dtype == ECHO_BF16 ? launch_ae_rope<bf16_t>((bf16_t*)x, ldx, rows, S, H, HD, cache, st)
+                                      : launch_ae_rope<float>((float*)x, ldx, rows, S, H, HD, cache, st));
+}
+int echo_op_dac_conv_in_snake(const float* x, int64_t T, int C, int k, const float* w, const float* b, const float* alpha, float* y, float* s,
+                              int64_t ld, void* stream) {
+  if (!x || !w || !b || !alpha || !y || !s) return op_refuse("echo_op_dac_conv_in_snake: null operand");
+  if (T < 1 || k < 1 || C < 4 || (C & 3) || ld < C || (ld & 3))
+    return op_refuse("echo_op_dac_conv_in_snake: needs T, k >= 1, C % 4 == 0, C >= 4, ld >= C and % 4 == 0");
+  return op_status(launch_conv_in_snake(x, (long)T, C, k, w, b, alpha, y, s, ld, (hipStream_t)stream));
+}
+int echo_op_dac_vq_argmax(const float* e, int64_t lde, int T, const float* cbn, const float* cb, int size, int32_t* idx, float* zst,
+                          int64_t ld_zst, float* gath, int64_t ld_g, void* stream) {
+  if (!e || !cbn || !cb || !idx || !zst || !gath) return op_refuse("echo_op_dac_vq_argmax: null operand");
+  if (T < 1 || size < 1 || lde < 8 || ld_zst < 8 || ld_g < 8 || ((uintptr_t)cbn & 15))
+    return op_refuse("echo_op_dac_vq_argmax: needs T, size >= 1, lde, ld_zst, ld_g >= 8, cbn 16-byte aligned");
+  return op_status(launch_vq_argmax(e, lde, T, cbn, cb, size, idx, zst, ld_zst, gath, ld_g, (hipStream_t)stream));
+}
+int echo_op_softmax(int dtype, void* s, int64_t ld, int rows_per_batch, int64_t total_rows, int ncols, int ncols_pad, const float* bias,
+                    int64_t bias_batch_stride, int heads_per_bias_row, int causal, int window, void* stream) {
+  if (!s) return op_refuse("echo_op_softmax: null operand");
+  if (!op_dtype_ok(dtype)) return op_refuse("echo_op_softmax: dtype must be ECHO_F32 or ECHO_BF16");
+  if (rows_per_batch < 1 || total_rows < 1 || total_rows % rows_per_batch || total_rows / rows_per_batch > 0x7fffffff || ncols < 1 ||
+      ncols_pad < ncols || ld < ncols_pad || heads_per_bias_row < 1 || window < 0)
+    return op_refuse("echo_op_softmax: needs rows_per_batch >= 1, total_rows a positive multiple of it, 1 <= ncols <= ncols_pad <= ld, "
+                     "heads_per_bias_row >= 1, window >= 0");
+  const int nbatch = (int)(total_rows / rows_per_batch);
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == ECHO_BF16) {
+    if (bias || causal != 1) return op_refuse("echo_op_softmax: the bf16 form is the causal-window softmax (bias == NULL, causal == 1)");
+    return op_status(launch_softmax_window_bf16((bf16_t*)s, ld, rows_per_batch, nbatch, ncols, ncols_pad, window, st));
+  }
+  return op_status(launch_softmax_f32((float*)s, ld, rows_per_batch, nbatch, ncols, ncols_pad, bias, bias_batch_stride, heads_per_bias_row,
+                                      causal ? 1 : 0, window, st));
+}
+
 // ---- on-device post-processing (postproc.hip)
 int echo_op_find_flattening_point(const float* latent, int64_t item_stride, int B, int T, int W, int window, float target, float std_threshold,
                                   int32_t* out_dev, void* stream) {

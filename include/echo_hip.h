@@ -438,6 +438,43 @@ int echo_op_headnorm_rope(int dtype, void* x, int64_t ldx, int64_t t_stride, int
 int echo_op_transpose_heads(int dtype, const void* v, int64_t ldv, void* vt, int64_t vt_ld, int64_t vt_b_stride, int B, int S,
                             int H, int HD, void* stream);
 
+/* -- the Fish S1-DAC's small kernels and the two softmaxes, one launch each (additive: ECHO_ABI_VERSION stays 8; tests/test_gpu_dac_kernels.py).
+ * Every wrapper refuses NULL operands, a dtype other than ECHO_F32 / ECHO_BF16 and the shapes named below with a non-zero status and launches
+ * nothing.  Pitches (ld*) are in elements.  "rows of S" = the causal padding restarts every S rows (one batch item).
+ *
+ * ConvNeXtBlock front half (autoencoder.py:362-364): y[t][c] = LayerNorm_C(b[c] + sum_k w[c][k] * x[t - 6 + k][c]) over the taps inside t's own
+ * item, T rows of S.  x, y, w (C, 7), b, lnw, lnb have `dtype`; bf16 rounds the conv output to bf16 before the LayerNorm and the result once.
+ * T >= 1, S >= 1, C % 4 == 0, 4 <= C <= 1024, ldx, ldy >= C and % 4 == 0.  Rows of an earlier item that the padding hides are not read. */
+int echo_op_dac_dwconv_ln(int dtype, const void* x, int64_t ldx, void* y, int64_t ldy, int T, int S, int C, const void* w, const void* b,
+                          const void* lnw, const void* lnb, float eps, void* stream);
+/* Decoder tail (autoencoder.py:994): y_f32[t] = tanh(bias + sum_kk w[kk] . x[t - (k - 1) + kk]) over the taps inside t's own item, T rows of S.
+ * x, w (k, C) have `dtype`, y is fp32 in both (bf16: the pre-activation and the result are rounded to bf16).
+ * T >= 1, S >= 1, C % 4 == 0, 4 <= C <= 128, 1 <= k <= 8, ldx >= C and % 4 == 0. */
+int echo_op_dac_conv_out_tanh(int dtype, const void* x, int64_t ldx, float* y_f32, int64_t T, int S, int C, int k, const void* w, float bias,
+                              void* stream);
+/* Snake (autoencoder.py:96-102), fp32: y[r][c] = x + sin(alpha[c] * x)^2 / (alpha[c] + 1e-9).  rows, C >= 1, ldx, ldy >= C. */
+int echo_op_dac_snake(const float* x, int64_t ldx, float* y, int64_t ldy, int64_t rows, int C, const float* alpha, void* stream);
+/* Interleaved-pair RoPE of the window transformers (autoencoder.py:815-826), in place on columns [0, H * HD) of x: row r has position r % S in
+ * cache (positions, HD / 2, 2) fp32 cos | sin.  The four products and the two sums are rounded separately (no FMA), bf16 once at the store.
+ * rows, S, H >= 1, HD >= 2 and even, ldx >= H * HD; the cache has at least min(rows, S) positions. */
+int echo_op_dac_rope(int dtype, void* x, int64_t ldx, int rows, int S, int H, int HD, const float* cache, void* stream);
+/* Encoder head (autoencoder.py:917), fp32: y[t][c] = b[c] + sum_kk w[c][kk] * x[t - (k - 1) + kk] (x = 0 before the first sample, which is
+ * not read), s[t][c] = Snake(y[t][c], alpha[c]); y and s share the pitch ld.  T, k >= 1, C % 4 == 0, C >= 4, ld >= C and % 4 == 0. */
+int echo_op_dac_conv_in_snake(const float* x, int64_t T, int C, int k, const float* w, const float* b, const float* alpha, float* y, float* s,
+                              int64_t ld, void* stream);
+/* VectorQuantize.decode_latents (autoencoder.py:145-158), codebook_dim 8, fp32: idx[t] = the first argmax over the codes of
+ * -|e^ - c^|^2 (e^ = e[t] / max(|e[t]|, 1e-12), c^ = cbn, the L2-normalised codebook), zst[t][0..7] = e + (cb[idx] - e), gath[t][0..7] = cb[idx].
+ * T, size >= 1, lde, ld_zst, ld_g >= 8; cbn 16-byte aligned. */
+int echo_op_dac_vq_argmax(const float* e, int64_t lde, int T, const float* cbn, const float* cb, int size, int32_t* idx, float* zst,
+                          int64_t ld_zst, float* gath, int64_t ld_g, void* stream);
+/* Row softmax in place on scores s (total_rows, ld); row r is query r % rows_per_batch of batch r / rows_per_batch.  Columns ncols..ncols_pad-1
+ * come back as zeros, columns beyond ncols_pad stay.  causal: keys > query are masked; window > 0 also masks keys < query - window + 1.
+ * ECHO_F32 (softmax_f32_kernel): bias (may be NULL) adds bias[(batch / heads_per_bias_row) * bias_batch_stride + c] first (-inf masks a key).
+ * ECHO_BF16 (softmax_window_bf16_kernel): bias == NULL and causal == 1 are required; only the window's columns are read.
+ * rows_per_batch >= 1, total_rows a positive multiple of it, 1 <= ncols <= ncols_pad <= ld, heads_per_bias_row >= 1. */
+int echo_op_softmax(int dtype, void* s, int64_t ld, int rows_per_batch, int64_t total_rows, int ncols, int ncols_pad, const float* bias,
+                    int64_t bias_batch_stride, int heads_per_bias_row, int causal, int window, void* stream);
+
 /* ---- on-device post-processing; `*_host` arguments are host arrays of n <= 64 entries ----
  * inference.py:288-296 find_flattening_point for B latents (T, W) fp32 (item_stride floats apart): out_dev[b] = first frame whose
  * zero-extended `window` frames have unbiased std < std_threshold and |mean - target| < 0.1, T if none. */

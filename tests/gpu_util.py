@@ -108,6 +108,45 @@ def quant_rows_fp8(x: torch.Tensor):
     return q, s
 
 
+# ---- the DAC's small kernels and the two softmaxes (tests/test_gpu_dac_kernels.py): torch tensors in, one launch, L.check on the status.
+# Pitches default to the tensors' row strides; T / rows / C are explicit because the buffers carry sentinel rows and columns.
+def dac_dwconv_ln(x, y, T, S, C, w, b, lnw, lnb, eps=1e-6, ldx=None, ldy=None):
+    L.check(lib().echo_op_dac_dwconv_ln(code(x), x.data_ptr(), x.stride(0) if ldx is None else ldx, y.data_ptr(),
+                                        y.stride(0) if ldy is None else ldy, T, S, C, w.data_ptr(), b.data_ptr(), lnw.data_ptr(), lnb.data_ptr(),
+                                        eps, stream()))
+
+
+def dac_conv_out_tanh(x, y_f32, T, S, C, k, w, bias, ldx=None):
+    L.check(lib().echo_op_dac_conv_out_tanh(code(x), x.data_ptr(), x.stride(0) if ldx is None else ldx, y_f32.data_ptr(), T, S, C, k, w.data_ptr(),
+                                            float(bias), stream()))
+
+
+def dac_snake(x, y, rows, C, alpha):
+    L.check(lib().echo_op_dac_snake(x.data_ptr(), x.stride(0), y.data_ptr(), y.stride(0), rows, C, alpha.data_ptr(), stream()))
+
+
+def dac_rope(x, rows, S, H, HD, cache, col_off=0):
+    """In place on columns [col_off, col_off + H * HD) of x (rows, ldx)."""
+    L.check(lib().echo_op_dac_rope(code(x), x.data_ptr() + col_off * x.element_size(), x.stride(0), rows, S, H, HD, cache.data_ptr(), stream()))
+
+
+def dac_conv_in_snake(x, T, C, k, w, b, alpha, y, s, x_off=0):
+    """x: 1-D fp32 samples, the first one at element x_off; y and s share their pitch."""
+    assert y.stride(0) == s.stride(0)
+    L.check(lib().echo_op_dac_conv_in_snake(x.data_ptr() + 4 * x_off, T, C, k, w.data_ptr(), b.data_ptr(), alpha.data_ptr(), y.data_ptr(),
+                                            s.data_ptr(), y.stride(0), stream()))
+
+
+def dac_vq_argmax(e, T, cbn, cb, size, idx, zst, gath):
+    L.check(lib().echo_op_dac_vq_argmax(e.data_ptr(), e.stride(0), T, cbn.data_ptr(), cb.data_ptr(), size, idx.data_ptr(), zst.data_ptr(),
+                                        zst.stride(0), gath.data_ptr(), gath.stride(0), stream()))
+
+
+def softmax(s, rows_per_batch, total_rows, ncols, ncols_pad, bias=None, bias_batch_stride=0, heads_per_bias_row=1, causal=0, window=0):
+    L.check(lib().echo_op_softmax(code(s), s.data_ptr(), s.stride(0), rows_per_batch, total_rows, ncols, ncols_pad, ptr(bias), bias_batch_stride,
+                                  heads_per_bias_row, causal, window, stream()))
+
+
 class FlushAlloc:
     """A dedicated hipMalloc whose payload ENDS exactly at the end of the allocation (sizes rounded up to 2 MiB, the granule the
     driver maps): a kernel that reads or writes even one byte past the operand touches the next, normally unmapped, page and
